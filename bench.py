@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark of the Vlaser hot path on MI355X (contract: one JSON line on rank 0).
 
-    python bench.py --gpus N --steps K --warmup W [--workload vla_chunk]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full] [--workload vla_chunk|sft|both]
 
 Workload `vla_chunk` = BASELINE.json configs[2]: Vlaser-2B-VLA image -> action-chunk forward (one 448x448 WidowX
 observation, 384-token prompt with 277 valid tokens, 7-DoF x 4-step chunk, 10 flow-matching Euler steps), batch 1,
@@ -10,10 +10,15 @@ bf16 storage / fp32 accumulate, synthetic inputs and deterministic random-init w
 Inference does not shard: N > 1 runs N independent replicas (one process per GPU, no data-path collective) and
 `value` is the whole-job rate = N*K chunks / max-over-ranks time ("scaling": "weak").
 
-Extra objects on the JSON line (tier contract 4):
+A plain run sets up, warms up, times the K steps, writes the outputs of the last step if asked (`--dump-outputs DIR`:
+DIR/<name>.npy, float32; inputs and weights are seeded, so two builds compare output for output) and prints the line.
+`--full` adds every side measurement (and makes `both` the default workload):
+  reference_signature : the same chunk through the valid_len call form, with and without the output ring
   roofline     : dominant kernel, algorithmic bytes per launch / HIP-event time per launch vs 8 TB/s HBM peak
+  phases, chunk_roofline : per-phase HIP-graph times, whole-chunk floor
   cpu_baseline : this repo's CPU oracle (a port of the reference's fp32 CPU path) timed on the host cores on a
                  bounded, depth-truncated sample and scaled linearly in depth (stated in `sample`)
+  sft, batched, two_in_flight, qa, qa_8b, vla_train : the other BASELINE configurations
 """
 import argparse
 import json
@@ -56,6 +61,14 @@ def _cpu_name():
 def _median(xs):
     xs = sorted(xs)
     return xs[len(xs) // 2]
+
+
+def dump_outputs(d, arrays):
+    """`--dump-outputs DIR`: what the timed call returned in its last step, one float32 DIR/<name>.npy per array."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + '.npy'), torch.as_tensor(t).detach().float().cpu().numpy())
 
 
 def cpu_baseline(vla_full, seed=0):
@@ -187,11 +200,12 @@ def sft_flops(cfg, S, R, n_tiles):
     return float(vit + proj + llm + attn + head)
 
 
-def sft_bench(rank, world, local, dist, steps, warmup=2):
+def sft_bench(rank, world, local, dist, steps, warmup=2, full=True, dump=None):
     """BASELINE configs[4]: Vlaser-2B SFT, data parallel, per-GPU micro-batch 1, T = 1 tile, S = 560 (48 + 256 image + 256 text),
     labels on the last 128 positions, ViT frozen, layer activations KEPT (1.1 GB; the reference recomputes them to fit 80 GB parts --
     `SFTModel(recompute=True)` restores that policy), bf16 params / fp32 AdamW, ZeRO-1 RCCL exchange.  ids / labels are handed over
-    as CPU tensors, as the reference's collator produces them: the step then runs without a host<->device round trip."""
+    as CPU tensors, as the reference's collator produces them: the step then runs without a host<->device round trip.
+    `full`: also the forward + backward time and the side numbers; `dump`: directory for the last step's loss and gradient norm."""
     from vlaser_amd import config as C, synth
     from vlaser_amd.sft import SFTModel
     dev = f'cuda:{local}'
@@ -248,17 +262,22 @@ def sft_bench(rank, world, local, dist, steps, warmup=2):
         dt = t.item()
     loss = float(out.loss)
     assert loss == loss, 'SFT loss is NaN'
-    # forward + backward alone (no gradient norm, no AdamW, no exchange): the part of the step an N-GPU ZeRO-1 rank runs unchanged (its AdamW is 1/N)
-    model.wait_optimizer()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        model.forward_backward(pv, ids, labels)
-    torch.cuda.synchronize()
-    fwd_bwd_ms = (time.perf_counter() - t0) / steps * 1e3
+    if dump is not None:
+        dump_outputs(dump, {'loss': out.loss, 'grad_norm': out.grad_norm})
+    fwd_bwd_ms = None
+    if full:
+        # forward + backward alone (no gradient norm, no AdamW, no exchange): the part of the step an N-GPU ZeRO-1 rank runs unchanged (its AdamW is 1/N)
+        model.wait_optimizer()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            model.forward_backward(pv, ids, labels)
+        torch.cuda.synchronize()
+        fwd_bwd_ms = (time.perf_counter() - t0) / steps * 1e3
     buckets_mb = [round((hi - lo) * 2 / 2 ** 20) for lo, hi in model.buckets]
     side = {}
-    if world == 1 and dist is None and os.environ.get('VLASER_BENCH_NO_SFT_SIDE') != '1':
+    side_numbers = full and world == 1 and dist is None and os.environ.get('VLASER_BENCH_NO_SFT_SIDE') != '1'
+    if side_numbers:
         # (a) per-device batch 4, the reference launcher's PER_DEVICE_BATCH_SIZE (internvl3_2b_dynamic_res_2nd_finetune_full.sh:47-67): one optimizer step over four samples.
         #     The kernels run one sample at a time (M = 560 rows each, fp32 gradient accumulation); AdamW and the norm are paid once per 2 240 tokens
         try:
@@ -286,7 +305,7 @@ def sft_bench(rank, world, local, dist, steps, warmup=2):
             side['micro_batch4'] = {'error': f'{type(e).__name__}: {e}'[:200]}
     del model
     torch.cuda.empty_cache()
-    if world == 1 and dist is None and os.environ.get('VLASER_BENCH_NO_SFT_SIDE') != '1':
+    if side_numbers:
         # (b) the reference's activation policy: grad_checkpoint on (BASELINE configs[4], SURVEY 8d, …2nd_finetune_full.sh:46) -- every layer's forward re-run inside the
         #     backward instead of 1.1 GB of kept activations; same values bit for bit (tests/test_sft_gpu.py)
         try:
@@ -318,8 +337,10 @@ def sft_bench(rank, world, local, dist, steps, warmup=2):
             side['recompute_ms_per_step'] = None
             side['recompute_error'] = f'{type(e).__name__}: {e}'[:200]
     fl = sft_flops(cfg, S, R - 1 + 1, 1)
+    if fwd_bwd_ms is not None:
+        side.update(fwd_bwd_ms=round(fwd_bwd_ms, 2), fwd_bwd_mfma_frac=round(fl / (fwd_bwd_ms * 1e-3) / 2.5e15, 4))
     return {'metric': 'sft_tokens_per_sec', 'value': round(world * steps * S / dt, 1), 'unit': 'tokens/s', 'ms_per_step': round(dt / steps * 1e3, 2),
-            'steps': steps, 'tokens_per_rank_step': S, 'last_loss': round(loss, 4), 'fwd_bwd_ms': round(fwd_bwd_ms, 2),
+            'steps': steps, 'tokens_per_rank_step': S, 'last_loss': round(loss, 4),
             'parallelism': f'dp{world} (ZeRO-1: bucketed RCCL reduce-scatter(mean, bf16) issued from the backward + all-gather of updated params)',
             'exchange': {'bucket_mib': buckets_mb, 'NCCL_ALGO': os.environ.get('NCCL_ALGO', 'default'), 'NCCL_PROTO': os.environ.get('NCCL_PROTO', 'default'),
                          'NCCL_MAX_NCHANNELS': os.environ.get('NCCL_MAX_NCHANNELS', 'unset = RCCL default (chosen: profiles/r05_rccl_contention.md section 4)'),
@@ -327,8 +348,7 @@ def sft_bench(rank, world, local, dist, steps, warmup=2):
                          'contention_model': {'source': 'profiles/r05_rccl_contention.md', 'fwd_bwd_stretch_by_channel_workgroups': {'1': 1.13, '8': 1.23, '16': 1.28, '32': 1.34, '64': 1.46},
                                               'both_streams_cu_masked': 1.13, 'predicted_fwd_bwd_ms_at_8_gpus': [16.4, 17.7]},
                          'gradient_bytes_per_rank': 3570e6 if world > 1 else 0, **exchange_info},
-            'gflop_per_rank_step': round(fl / 1e9, 1), 'mfma_frac': round(fl * world * steps / dt / (world * 2.5e15), 4),
-            'fwd_bwd_mfma_frac': round(fl / (fwd_bwd_ms * 1e-3) / 2.5e15, 4), **side}
+            'gflop_per_rank_step': round(fl / 1e9, 1), 'mfma_frac': round(fl * world * steps / dt / (world * 2.5e15), 4), **side}
 
 
 def main():
@@ -336,14 +356,20 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--workload', default='both', choices=['vla_chunk', 'sft', 'both'])
+    ap.add_argument('--workload', default=None, choices=['vla_chunk', 'sft', 'both'], help='default: vla_chunk, or both with --full')
     ap.add_argument('--sft-steps', type=int, default=10)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--no-8b', action='store_true', help='skip the Vlaser-8B x 13-tile side numbers (BASELINE configs[3])')
+    ap.add_argument('--full', action='store_true', help='also every side measurement (call forms, phases, roofline, CPU baselines, SFT side numbers, the other '
+                                                        'BASELINE configurations); a plain run times the headline alone')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what the last timed call returned as DIR/<name>.npy (float32)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baselines')
+    ap.add_argument('--no-roofline', action='store_true', help='--full: skip phases and roofline')
+    ap.add_argument('--no-8b', action='store_true', help='--full: skip the Vlaser-8B x 13-tile side numbers (BASELINE configs[3])')
 
     ap.add_argument('--dry-run', action='store_true', help='rendezvous only (gloo, no GPU work): checks the N-rank launch path')
     a = ap.parse_args()
+    if a.steps < 1 or a.sft_steps < 1:
+        ap.error('--steps and --sft-steps must be >= 1')
+    workload = a.workload or ('both' if a.full else 'vla_chunk')
 
     if a.gpus > 1 and 'RANK' not in os.environ:
         # `python bench.py --gpus N`: this parent never touches the GPU; it starts N ranks (one process per GPU) and relays rank 0's line
@@ -365,8 +391,8 @@ def main():
 
     torch.set_grad_enabled(False)
     sft_line = None
-    if a.workload == 'sft':
-        sft_line = sft_bench(rank, world, local, dist, a.sft_steps)
+    if workload == 'sft':
+        sft_line = sft_bench(rank, world, local, dist, a.sft_steps, full=a.full, dump=a.dump_outputs if rank == 0 else None)
         if rank == 0:
             sft_line.update({'n_gpus': world, 'warmup': 2, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16',
                              'data': 'synthetic', 'config': {'workload': 'Vlaser-2B SFT, per-GPU micro-batch 1, S=560 (BASELINE configs[4])'}})
@@ -413,6 +439,8 @@ def main():
         dt = t.item()
     assert torch.isfinite(out).all()
     model.check_errors()                                             # the device-side mask check of every timed call came back clean
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {'actions': out})               # the action chunk [1, 4, 7] of the last timed call
 
     def _time_calls(fn, n):
         fn(); torch.cuda.synchronize()
@@ -424,13 +452,6 @@ def main():
 
     line = None
     if rank == 0:
-        # side timings of the same chunk through the two other call forms (never `value`): the valid_len extension with a fresh result, and with the
-        # zero-copy result ring switched on (output_ring = 4: a view that is overwritten four calls later)
-        ext_ms, out_ext = _time_calls(call_ext, a.steps)
-        model.output_ring = 4
-        ring_ms, _ = _time_calls(call_ext, a.steps)
-        model.output_ring = 0
-        assert torch.equal(out_ext, out)
         line = {
             'metric': 'action_chunks_per_sec', 'value': round(world * a.steps / dt, 3), 'unit': 'action-chunks/s',
             'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': round(dt / a.steps * 1e3, 4),
@@ -443,6 +464,14 @@ def main():
                        'reference_mode': 'use_bf16=True (bf16 storage / fp32 accumulate: the mode the reference trains in, slurm/train_internvl.sh:35; its shipped eval '
                                          'config runs fp32, bridge_internvl_448.yaml:36)'},
         }
+    if rank == 0 and a.full:
+        # side timings of the same chunk through the two other call forms (never `value`): the valid_len extension with a fresh result, and with the
+        # zero-copy result ring switched on (output_ring = 4: a view that is overwritten four calls later)
+        ext_ms, out_ext = _time_calls(call_ext, a.steps)
+        model.output_ring = 4
+        ring_ms, _ = _time_calls(call_ext, a.steps)
+        model.output_ring = 0
+        assert torch.equal(out_ext, out)
         line['reference_signature'] = {'ms_per_chunk': round(dt / a.steps * 1e3, 4), 'is_headline': True,
                                        'valid_len_extension_ms': round(ext_ms, 4), 'valid_len_extension_output_ring4_ms': round(ring_ms, 4),
                                        'note': 'the dense masks are checked and valid_len counted ON the device by the one staging launch (vlaser_vla_stage, ABI 6); '
@@ -483,7 +512,7 @@ def main():
     # ---- SFT line (BASELINE configs[4]) AFTER the headline has been timed: the gradient exchange is the only part of this file that
     # has never run on more than one physical GPU, so it must not be able to take the headline down with it.  Any rank that fails
     # skips ahead; rank 0 runs a watchdog that prints the headline line and leaves if the exchange hangs on a missing peer.
-    if a.workload == 'both':
+    if workload == 'both':
         del model
         torch.cuda.empty_cache()
         watchdog = None
@@ -499,20 +528,20 @@ def main():
             watchdog.daemon = True
             watchdog.start()
         try:
-            sft_line = sft_bench(rank, world, local, dist, a.sft_steps)
+            sft_line = sft_bench(rank, world, local, dist, a.sft_steps, full=a.full)
         except Exception as e:                                   # noqa: BLE001  (reported in the line, never fatal for the headline)
             sft_line = {'error': f'{type(e).__name__}: {e}'[:400]}
         if watchdog is not None:
             watchdog.cancel()
     if rank == 0:
         if sft_line is not None:
-            if world == 1 and dist is None and 'error' not in sft_line and os.environ.get('VLASER_BENCH_NO_FORCED_DP') != '1':
+            if a.full and world == 1 and dist is None and 'error' not in sft_line and os.environ.get('VLASER_BENCH_NO_FORCED_DP') != '1':
                 # both exchange modes: torch's ProcessGroupNCCL, and RCCL's C API on a CU-masked stream with the compute streams on the complement
                 sft_line['forced_dp_world1_ms'] = {m: _forced_dp_world1(a.sft_steps, m) for m in ('pg', 'capi')}
-            if world == 1 and not a.no_cpu_baseline and 'error' not in sft_line:
+            if a.full and world == 1 and not a.no_cpu_baseline and 'error' not in sft_line:
                 sft_line['cpu_baseline'] = sft_cpu_baseline(vla.base)
             line['sft'] = sft_line
-        if world == 1 and a.workload == 'both':
+        if a.full and world == 1 and workload == 'both':
             line['batched'] = batched_chunks(vla, dev, a.steps)
             line['two_in_flight'] = two_in_flight(vla, dev, a.steps)
             line['qa'] = qa_bench(local)
@@ -534,7 +563,7 @@ def _forced_dp_world1(steps, mode='pg'):
     cannot be added to this one after the fact), its own line parsed; None (with the reason) when the child fails."""
     env = dict(os.environ, VLASER_FORCE_DP='1', VLASER_DP_EXCHANGE=mode, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(_free_port()), RANK='0', WORLD_SIZE='1', LOCAL_RANK='0')
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--workload', 'sft', '--sft-steps', str(steps), '--no-cpu-baseline'], env=env, capture_output=True,
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--workload', 'sft', '--sft-steps', str(steps), '--full', '--no-cpu-baseline'], env=env, capture_output=True,
                            text=True, timeout=600)
         ln = next((x for x in reversed(r.stdout.splitlines()) if x.startswith('{')), None)
         if ln is None:

@@ -41,6 +41,12 @@ def test_world_mismatch_fails_loudly():
     assert p.returncode != 0 and 'WORLD_SIZE=1' in (p.stderr + p.stdout)
 
 
+def test_steps_must_be_positive():
+    """`--steps` is the number of timed steps and `ms_per_step` divides by it: zero is refused before any work."""
+    p = subprocess.run([sys.executable, BENCH, '--gpus', '1', '--steps', '0', '--dry-run'], env=_env(), capture_output=True, text=True, timeout=600)
+    assert p.returncode != 0 and '--steps' in p.stderr
+
+
 def test_failed_rank_after_the_line_is_a_failed_run():
     """a rank that dies (or the SFT watchdog firing) after rank 0 printed its line must not be reported as success."""
     e = _env()

@@ -1,7 +1,7 @@
 """GPU-box helper: one bench.py run, the figures an A/B needs on one line.  usage: python tools/gpu/ab_line.py <label> [bench.py args...]"""
 import json, subprocess, sys
 label, args = sys.argv[1], sys.argv[2:]
-out = subprocess.run([sys.executable, 'bench.py', '--no-cpu-baseline', '--no-8b'] + args, capture_output=True, text=True).stdout.strip().splitlines()
+out = subprocess.run([sys.executable, 'bench.py', '--full', '--no-cpu-baseline', '--no-8b'] + args, capture_output=True, text=True).stdout.strip().splitlines()
 d = json.loads(out[-1])
 ph, qa, sft = d.get('phases') or {}, d.get('qa') or {}, d.get('sft') or {}
 print(label, 'chunk_ms', d.get('ms_per_step'), 'euler_us', ph.get('euler_us_per_layer_step'), 'vit', ph.get('vit_ms'), 'prefill', ph.get('prefill_ms'),

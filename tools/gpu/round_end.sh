@@ -4,7 +4,7 @@
 tag="${1:-rXX}"
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
-timeout 1500 python bench.py > "gpurun_out/${tag}_bench_line.json" 2> "gpurun_out/${tag}_bench.err"; tail -c 300 "gpurun_out/${tag}_bench.err" | tail -2
+(cd "$_" && timeout 1500 python ../bench.py --full > "${tag}_bench_line.json" 2> "${tag}_bench.err"; tail -c 300 "${tag}_bench.err" | tail -2)
 cd /tmp && export TMPDIR=/tmp
 TAIL_MS=140 bash "$GRAFT_REPO_ROOT/tools/run_profile.sh" "${tag}_sft" --workload sft --sft-steps 10 --no-cpu-baseline --no-roofline --no-8b > /dev/null
 TAIL_MS=200 bash "$GRAFT_REPO_ROOT/tools/run_profile.sh" "${tag}_chunk" --workload vla_chunk --steps 20 --warmup 3 --no-cpu-baseline --no-roofline --no-8b > /dev/null

@@ -26,7 +26,7 @@ def sweep():
         env.pop('NCCL_MAX_NCHANNELS', None)
         if ch != 'default':
             env['NCCL_MAX_NCHANNELS'] = ch
-        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'sft', '--sft-steps', '8', '--no-cpu-baseline'], env=env, capture_output=True, text=True,
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'sft', '--sft-steps', '8', '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True,
                            timeout=900)
         line = next((ln for ln in reversed(r.stdout.splitlines()) if ln.startswith('{')), None)
         if line is None:
