@@ -659,7 +659,8 @@ extern "C" int vlaser_embed_scatter_add(const int64_t* ids, const int32_t* rank,
 __global__ __launch_bounds__(256) void gelu_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy, bf16_t* __restrict__ dx, long long n) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     const float v = bf16_to_f32(x[i]);
-    const float cdf = 0.5f * (1.0f + erff(v * 0.70710678118654752f));
+    // Phi(v) = erfc(-v / sqrt2) / 2: 0.5 (1 + erf) cancels for v < -5 (Phi(-5.5625) came out 0 against 1.3e-8, 3 % of gelu' -- 2.6 bf16 ulps)
+    const float cdf = 0.5f * erfcf(-v * 0.70710678118654752f);
     const float pdf = 0.3989422804014327f * __expf(-0.5f * v * v);
     dx[i] = f32_to_bf16(bf16_to_f32(dy[i]) * (cdf + v * pdf));
   }
@@ -1088,15 +1089,22 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= S) return;
   const size_t ro = (size_t)row * C;
-  float sx = 0.f, sxx = 0.f;
+  float sx = 0.f;
   for (int c = lane * 8; c < C; c += 512) {
     const u32x4 xv = ld_global_16(x + ro + c);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { const float a = bf16lo_to_f32(xv[j]), b = bf16hi_to_f32(xv[j]); sx += a + b; sxx += a * a + b * b; }
+    for (int j = 0; j < 4; ++j) sx += bf16lo_to_f32(xv[j]) + bf16hi_to_f32(xv[j]);
   }
-  sx = wave_sum(sx); sxx = wave_sum(sxx);
-  const float mean = sx / (float)C;
-  const float rs = rsqrtf(fmaxf(sxx / (float)C - mean * mean, 0.f) + eps);
+  const float mean = wave_sum(sx) / (float)C;
+  // two-pass variance, as the forward LayerNorm (misc.hip) and rowstat_kernel: the one-pass E[x^2] - mean^2 is 0 in fp32 once the variance falls
+  // under the resolution of mean^2 (a near-constant row of 1000 with one channel a bf16 step off: rs = 1/sqrt(eps) = 1000 instead of 8)
+  float vs = 0.f;
+  for (int c = lane * 8; c < C; c += 512) {
+    const u32x4 xv = ld_global_16(x + ro + c);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const float a = bf16lo_to_f32(xv[j]) - mean, b = bf16hi_to_f32(xv[j]) - mean; vs += a * a + b * b; }
+  }
+  const float rs = rsqrtf(wave_sum(vs) / (float)C + eps);
   float sg = 0.f, sgx = 0.f;
   for (int c = lane * 8; c < C; c += 512) {
     const u32x4 xv = ld_global_16(x + ro + c), gv = ld_global_16(dy + ro + c), wv = ld_global_16(w + c);
