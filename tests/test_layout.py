@@ -199,6 +199,41 @@ def test_weight_packing_roundtrip():
         assert torch.equal(v[0, 1, 3, 0, 1, 2, 5], W[32 + 16 + 5, k0:k0 + 8])
 
 
+def test_layer_codec_roundtrip():
+    """HF names -> kernel layout -> HF names through the trainers' codec (param_group.py) returns every tensor bit for bit: one GQA decoder layer
+    with head_dim 128 (12 query / 2 key-value heads, hidden 1536, MLP 8960) and the projector mlp1, random bf16 tensors."""
+    from types import SimpleNamespace
+    from vlaser_amd import param_group as PG
+    llm = SimpleNamespace(hidden_size=1536, intermediate_size=8960, num_attention_heads=12, num_key_value_heads=2, head_dim=128)
+    H, I, nq, nkv, hd, C4 = 1536, 8960, 12, 2, 128, 4096
+    gen = torch.Generator().manual_seed(7)
+    rnd = lambda *s: torch.randn(*s, generator=gen).to(torch.bfloat16)
+    p = 'language_model.model.layers.3.'
+    sd = {p + 'self_attn.q_proj.weight': rnd(nq * hd, H), p + 'self_attn.q_proj.bias': rnd(nq * hd),
+          p + 'self_attn.k_proj.weight': rnd(nkv * hd, H), p + 'self_attn.k_proj.bias': rnd(nkv * hd),
+          p + 'self_attn.v_proj.weight': rnd(nkv * hd, H), p + 'self_attn.v_proj.bias': rnd(nkv * hd),
+          p + 'self_attn.o_proj.weight': rnd(H, nq * hd), p + 'mlp.gate_proj.weight': rnd(I, H), p + 'mlp.up_proj.weight': rnd(I, H),
+          p + 'mlp.down_proj.weight': rnd(H, I), p + 'input_layernorm.weight': rnd(H), p + 'post_attention_layernorm.weight': rnd(H)}
+    specs = PG.decoder_layer_specs(llm)
+    assert [nm for nm, _ in specs] == list(PG.DECODER_LAYER_NAMES)
+    assert dict(specs)['wqkv'] == ((nq + 2 * nkv) * hd, H) and dict(specs)['wgu'] == (2 * I, H) and dict(specs)['wo'] == (H, nq * hd)
+    views = {'l3.' + nm: torch.zeros(shp, dtype=torch.bfloat16) for nm, shp in specs}
+    PG.pack_decoder_layer(sd, p, views, 'l3.', hd)
+    assert not torch.equal(views['l3.wqkv'][:nq * hd], sd[p + 'self_attn.q_proj.weight'])      # the kernel layout IS a permutation, not the identity
+    back = PG.unpack_decoder_layer(views, 'l3.', p, llm)
+    assert sorted(back) == sorted(sd)
+    for k in sd:
+        assert back[k].dtype == torch.bfloat16 and torch.equal(back[k], sd[k]), k
+    msd = {k: rnd(*shp) for (nm, k), (nm2, shp) in zip(PG.MLP1_KEYS, PG.mlp1_specs(H, C4))}
+    assert msd['mlp1.1.weight'].shape == (H, C4) and msd['mlp1.0.bias'].shape == (C4,) and msd['mlp1.3.weight'].shape == (H, H)
+    mviews = {'mlp1.' + nm: torch.zeros(shp, dtype=torch.bfloat16) for nm, shp in PG.mlp1_specs(H, C4)}
+    PG.pack_mlp1(msd, mviews)
+    mback = PG.unpack_mlp1(mviews)
+    assert sorted(mback) == sorted(msd)
+    for k in msd:
+        assert torch.equal(mback[k], msd[k]), k
+
+
 def test_vla_checkpoint_keys_of_the_reference_canonicalize():
     """Golden G9 = the key names / shapes of the reference's own PiZero module tree (built on the meta device by
     tools/gen_golden_vla_keys.py).  Every key must canonicalise onto a tensor the loader consumes (or onto the short list of

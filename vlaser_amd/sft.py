@@ -24,9 +24,10 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib as L
-from . import dp, ops
+from . import backward, ops
 from .config import VlaserConfig
 from .engine import BF, KVCache, VitEngine
+from .param_group import FlatParams, ParamGroup, behind_current, cut_buckets, decoder_layer_specs, mlp1_specs, pack_decoder_layer, pack_mlp1, unpack_decoder_layer, unpack_mlp1
 
 F32 = torch.float32
 
@@ -54,56 +55,13 @@ def cosine_lr(step, total_steps, base_lr, warmup_ratio=0.03):
     return base_lr * max(0.0, 0.5 * (1.0 + math.cos(math.pi * prog)))
 
 
-class FlatParams:
-    """Flat bf16 parameter / gradient buffers with named views (+ fp32 master / moments for the local ZeRO-1 shard)."""
-
-    def __init__(self, device):
-        self.device = device
-        self.specs = []          # (name, shape, offset)
-        self.n = 0
-
-    def add(self, name, shape):
-        numel = 1
-        for s in shape:
-            numel *= s
-        self.specs.append((name, tuple(shape), self.n))
-        self.n += (numel + 127) // 128 * 128          # 256-byte aligned views
-        return len(self.specs) - 1
-
-    def align(self, multiple):
-        """Pad so that the next tensor starts at a multiple of `multiple` elements (bucket boundaries: every ZeRO-1 bucket
-        then divides evenly over the ranks and the collectives run in place, without staging copies)."""
-        self.n = (self.n + multiple - 1) // multiple * multiple
-
-    def finalize(self, pad_to=1):
-        self.n = (self.n + pad_to - 1) // pad_to * pad_to
-        self.p = torch.zeros(self.n, dtype=BF, device=self.device)
-        self.g = torch.zeros(self.n, dtype=BF, device=self.device)
-        self.view = {}
-        self.gview = {}
-        for name, shape, off in self.specs:
-            numel = 1
-            for s in shape:
-                numel *= s
-            self.view[name] = self.p[off:off + numel].view(shape)
-            self.gview[name] = self.g[off:off + numel].view(shape)
-
-    def offset_of(self, name):
-        for n, _, off in self.specs:
-            if n == name:
-                return off
-        raise KeyError(name)
-
-
 def plan_flat_layout(cfg, world, bucket_layers=4, device='cpu'):
     """The flat parameter / gradient layout of the SFT step and its gradient buckets, without allocating anything: (FlatParams before `finalize`,
     [(lo, hi)]).  Order = the order the backward completes the gradients: [head (+ zero pad rows up to a multiple of 64) + final norm], the layers
     last to first in groups of `bucket_layers`, [embedding + projector]; every bucket boundary is a multiple of 128 * world elements, so each ZeRO-1
     bucket divides evenly over the ranks and the RCCL collectives run in place (dp.py).  Also used by the CPU test of the world-8 shard plan."""
     llm = cfg.llm
-    H, I, V = llm.hidden_size, llm.intermediate_size, llm.vocab_size
-    nq, nkv, hd = llm.num_attention_heads, llm.num_key_value_heads, llm.head_dim
-    NQ = (nq + 2 * nkv) * hd
+    H, V = llm.hidden_size, llm.vocab_size
     Vp = (V + 63) // 64 * 64
     fp = FlatParams(device)
     fp.add('head', (V, H))
@@ -112,13 +70,11 @@ def plan_flat_layout(cfg, world, bucket_layers=4, device='cpu'):
     fp.add('norm', (H,))
     fp.align(128 * world)                     # end of bucket 0 (head + final norm)
     for i in reversed(range(llm.num_hidden_layers)):
-        for nm, shp in [('wqkv', (NQ, H)), ('bqkv', (NQ,)), ('wo', (H, nq * hd)), ('wgu', (2 * I, H)), ('wdown', (H, I)), ('ln_in', (H,)),
-                        ('ln_post', (H,))]:
+        for nm, shp in decoder_layer_specs(llm):
             fp.add(f'l{i}.{nm}', shp)
     fp.align(128 * world)                     # layer buckets are whole layers: already multiples for world <= 8, keep it explicit
     fp.add('embed', (V, H))
-    C4 = cfg.vision.hidden_size * 4
-    for nm, shp in [('m0w', (C4,)), ('m0b', (C4,)), ('m1w', (H, C4)), ('m1b', (H,)), ('m3w', (H, H)), ('m3b', (H,))]:
+    for nm, shp in mlp1_specs(H, cfg.vision.hidden_size * 4):
         fp.add('mlp1.' + nm, shp)
     n_total = (fp.n + 128 * world * 8 - 1) // (128 * world * 8) * (128 * world * 8)       # what finalize(pad_to=128 * world * 8) makes of it
     bounds = [fp.offset_of(f'l{llm.num_hidden_layers - 1}.wqkv')]
@@ -127,15 +83,10 @@ def plan_flat_layout(cfg, world, bucket_layers=4, device='cpu'):
         bounds.append(fp.offset_of(f'l{layers_rev[j]}.wqkv'))
     bounds.append(fp.offset_of('embed'))
     bounds.append(n_total)
-    buckets, lo = [], 0
-    for hi in bounds:
-        if hi > lo:
-            buckets.append((lo, hi))
-            lo = hi
-    return fp, buckets
+    return fp, cut_buckets(bounds)
 
 
-class SFTModel:
+class SFTModel(ParamGroup):
     """Trainable Vlaser-2B SFT step (per rank).  `step(pixel_values, input_ids, labels)` runs forward, backward, the
     gradient exchange and the optimizer update and returns the (rank-local) loss."""
 
@@ -167,6 +118,13 @@ class SFTModel:
         if self.attn_bwd_mode not in ('fused', 'materialised'):
             raise ValueError(f'VLASER_SFT_ATTN_BWD={self.attn_bwd_mode!r}: fused | materialised')
         self.ag_events = {}                       # bucket -> event of its last parameter all-gather (data parallel only)
+        self.opt_stream = self.comm_stream = None  # made by load_state_dict (`_alloc_workspace`)
+        # per-step state of the gradient norm taken from the producers (`_run_weighted_main`) and of the buffers that are cleared lazily
+        self._fused_norm = self._norm_early = False
+        self._norm_buckets_seen = 0
+        self.norm_parts = None
+        self._embed_touched = None
+        self._head_pad_Rp = None
         self.overlap_allgather = os.environ.get('VLASER_SFT_NO_AG_OVERLAP') != '1'
         self.overlap_optimizer = os.environ.get('VLASER_SFT_NO_OPT_OVERLAP') != '1'
         self.step_count = 0
@@ -182,14 +140,11 @@ class SFTModel:
         self._embed_touched = None
         self.vit = VitEngine(sd, cfg, dev, max_tiles=self.max_tiles)     # frozen (freeze_backbone True)
         self.frozen_sd = {k: v.detach().to('cpu') for k, v in sd.items() if k.startswith('vision_model.')}      # for save_pretrained
-        H, I, V = llm.hidden_size, llm.intermediate_size, llm.vocab_size
-        nq, nkv, hd = llm.num_attention_heads, llm.num_key_value_heads, llm.head_dim
-        NQ = (nq + 2 * nkv) * hd
+        H, V = llm.hidden_size, llm.vocab_size
         self.Vp = (V + 63) // 64 * 64
-        fp, self.buckets = plan_flat_layout(cfg, self.world, self.bucket_layers, dev)
+        fp, buckets = plan_flat_layout(cfg, self.world, self.bucket_layers, dev)
         fp.finalize(pad_to=128 * self.world * 8)
-        assert fp.n == self.buckets[-1][1], 'plan_flat_layout and FlatParams.finalize disagree on the padded length'
-        self.fp = fp
+        assert fp.n == buckets[-1][1], 'plan_flat_layout and FlatParams.finalize disagree on the padded length'
         o_head = fp.offset_of('head')
         self.head_full = fp.p[o_head:o_head + self.Vp * H].view(self.Vp, H)      # [Vp, H]: lm_head rows + the zero pad rows
         g = lambda k: sd[k].to(device=dev, dtype=BF)
@@ -197,32 +152,11 @@ class SFTModel:
         fp.view['norm'].copy_(g('language_model.model.norm.weight'))
         fp.view['embed'].copy_(g('language_model.model.embed_tokens.weight'))
         for i in range(llm.num_hidden_layers):
-            p = f'language_model.model.layers.{i}.'
-            wqkv, bqkv = ops.pack_qkv(g(p + 'self_attn.q_proj.weight'), g(p + 'self_attn.k_proj.weight'), g(p + 'self_attn.v_proj.weight'),
-                                      g(p + 'self_attn.q_proj.bias'), g(p + 'self_attn.k_proj.bias'), g(p + 'self_attn.v_proj.bias'), hd)
-            fp.view[f'l{i}.wqkv'].copy_(wqkv); fp.view[f'l{i}.bqkv'].copy_(bqkv)
-            fp.view[f'l{i}.wo'].copy_(g(p + 'self_attn.o_proj.weight'))
-            fp.view[f'l{i}.wgu'].copy_(ops.pack_gate_up(g(p + 'mlp.gate_proj.weight'), g(p + 'mlp.up_proj.weight')))
-            fp.view[f'l{i}.wdown'].copy_(g(p + 'mlp.down_proj.weight'))
-            fp.view[f'l{i}.ln_in'].copy_(g(p + 'input_layernorm.weight'))
-            fp.view[f'l{i}.ln_post'].copy_(g(p + 'post_attention_layernorm.weight'))
-        for nm, k in [('m0w', 'mlp1.0.weight'), ('m0b', 'mlp1.0.bias'), ('m1w', 'mlp1.1.weight'), ('m1b', 'mlp1.1.bias'),
-                      ('m3w', 'mlp1.3.weight'), ('m3b', 'mlp1.3.bias')]:
-            fp.view['mlp1.' + nm].copy_(g(k))
-        # ZeRO-1: every rank owns the slice [lo + r*len/N, lo + (r+1)*len/N) of each bucket (bucket lengths are multiples of 128;
-        # uneven division is handled by padding the reduce-scatter input)
-        assert all((hi - lo) % (128 * self.world) == 0 for lo, hi in self.buckets), 'ZeRO-1 buckets must divide evenly over the ranks'
-        self.shards = dp.plan_shards(self.buckets, self.world, self.rank)
-        n_shard = sum(hi - lo for lo, hi, _ in self.shards)
-        self.master = torch.zeros(n_shard, dtype=F32, device=dev)
-        self.m = torch.zeros(n_shard, dtype=F32, device=dev)
-        self.v = torch.zeros(n_shard, dtype=F32, device=dev)
-        o = 0
-        self.shard_off = []
-        for lo, hi, _ in self.shards:
-            self.master[o:o + hi - lo].copy_(fp.p[lo:hi].float())
-            self.shard_off.append(o)
-            o += hi - lo
+            pack_decoder_layer(sd, f'language_model.model.layers.{i}.', fp.view, f'l{i}.', llm.head_dim)
+        pack_mlp1(sd, fp.view)
+        self.init_group(fp, [hi for _, hi in buckets], self.world, self.rank)
+        # layer buckets hold the layers in reverse order, `bucket_layers` each (bucket 0 = lm_head + final norm, bucket 1 = the last layers)
+        self.bucket_of_layer = {li: 1 + (llm.num_hidden_layers - 1 - li) // self.bucket_layers for li in range(llm.num_hidden_layers)}
         self._alloc_workspace()
         return self
 
@@ -273,7 +207,6 @@ class SFTModel:
         self.gnorm2 = torch.zeros(1, dtype=F32, device=dev)
         self.rank_ws = torch.zeros(S, dtype=torch.int32, device=dev)
         self.pos_all = torch.arange(S, dtype=torch.int32, device=dev)
-        self.gacc = None                                            # fp32 gradient accumulator (allocated by the first multi-sample step)
         self._alloc_projector_ws()
         # The exchange (data parallel only).  VLASER_DP_EXCHANGE=pg (default): torch's ProcessGroupNCCL from a comm stream.  =capi: RCCL's C API on a communicator and a
         # stream of this package's own (rccl_capi.py), that stream CU-masked to the last VLASER_DP_COMM_CUS CUs (default 32; 0 = no masks) and EVERY compute stream of the
@@ -355,9 +288,9 @@ class SFTModel:
 
     def wait_optimizer(self):
         """Make the current stream wait for parameter updates / all-gathers still in flight on the side streams."""
-        if getattr(self, 'opt_stream', None) is not None:
+        if self.opt_stream is not None:
             torch.cuda.current_stream().wait_stream(self.opt_stream)
-        if self.dp_active and getattr(self, 'comm_stream', None) is not None:
+        if self.dp_active and self.comm_stream is not None:
             torch.cuda.current_stream().wait_stream(self.comm_stream)
 
     def _wait_params(self, b):
@@ -415,7 +348,7 @@ class SFTModel:
 
     def _ssq(self, name):
         """The slot slice the producer of gradient `name` fills, or None when this step takes the norm from the gradient buffer."""
-        if not getattr(self, '_fused_norm', False):
+        if not self._fused_norm:
             return None
         lo, cap = self.norm_slot[name]
         return self.norm_parts[lo:lo + cap]
@@ -423,7 +356,7 @@ class SFTModel:
     def _head_pads(self, R, Rp):
         """The lm_head's two row-padded operands ([ceil64(R), H] inputs, [ceil64(R), Vp] dlogits), allocated once per padded row count; their rows
         R..Rp must be zero (they enter the weight gradient's contraction): cleared when R changes -- the kernels only ever write rows < R."""
-        if getattr(self, '_head_pad_Rp', None) != Rp:
+        if self._head_pad_Rp != Rp:
             self._x_pad = torch.zeros(Rp, self.llm.hidden_size, dtype=BF, device=self.device)
             self._dlog_pad = torch.zeros(Rp, self.Vp, dtype=BF, device=self.device)
             self._head_pad_Rp, self._head_pad_R = Rp, R
@@ -474,27 +407,6 @@ class SFTModel:
             for b in (self.act, self.x2, self.ao, self.x1):
                 b[:, S:Sp].zero_()
         self._wgrad_pad_S = S
-
-    def _dgrad(self, dY, W, out, S, keep_slabs=False):
-        """out[S,K] = dY[S,N] @ W[N,K], W as the forward stores it (NN GEMM); long contractions over few output tiles run split-K.  `keep_slabs`: a
-        split-K product is NOT reduced -- returns (slabs, count) for a consumer that sums them itself (`vlaser_rmsnorm_bwd`'s dy_partials), else None."""
-        Nin, Kout = W.shape
-        # measured at S = 560, 1536 outputs (tools/micro/nn_lab.py): contraction <= 2048 -> one pass (11.5-14.6 us) beats split-K slabs +
-        # their reduction (9-11 + 5 us); longer contractions (8960 / 17920) keep split-K
-        sp = 1 if Nin <= 2048 else ops.gemm_splits(S, Kout, Nin, nn=True)
-        if sp > 1:
-            part = self.part[:sp * S * Kout]
-            ops.gemm_nn(L.EPI_PARTIAL, dY, W, out_f32=part, k_splits=sp)
-            if keep_slabs:
-                return part, sp
-            ops.reduce_norm(None, part, sp, S, Kout, out)
-        else:
-            ops.gemm_nn(L.EPI_NONE, dY, W, out=out)
-        return None
-
-    def _norm_wgrad(self, dy, x, out, S, Cc, mode=2, eps=1e-6):
-        ops.colsum_mul(dy, x, self.col, S, Cc, mode, eps, self.rowstat)
-        out.copy_(self.col[:Cc])
 
     # ------------------------------------------------------------------ forward of one layer with everything saved for its backward
     def _layer_forward(self, i, h_in, S, pos, x1_ready=False):
@@ -598,8 +510,8 @@ class SFTModel:
         # fill) instead of the table; anything else that wrote the bucket (gradient accumulation's finalize, a reduce-scatter) resets to the full clear
         # (only inside train_step's one-sample path -- `_fused_norm` -- where nothing but this function writes the gradient buffer between two calls; a direct
         # forward_backward() call, whose caller may do anything to fp.g in between, clears the table)
-        touched = getattr(self, '_embed_touched', None)
-        own = getattr(self, '_fused_norm', False) and os.environ.get('VLASER_SFT_EMBED_FULL_CLEAR') != '1'
+        touched = self._embed_touched
+        own = self._fused_norm and os.environ.get('VLASER_SFT_EMBED_FULL_CLEAR') != '1'
         if touched is not None and own:
             gv['embed'].index_fill_(0, touched, 0)
         else:
@@ -609,10 +521,7 @@ class SFTModel:
         C1 = cfg.vision.hidden_size
         G_ = cfg.vision.image_size // cfg.vision.patch_size
         ps_raw, ps_ln, z1, g1, feat = self.ps_raw[:nt], self.ps_ln[:nt], self.z1[:nt], self.g1[:nt], self.feat[:nt]
-        ops.pixel_shuffle(vit_w.h, ps_raw, T, G_, C1, 1 if cfg.ps_version == 'v1' else 0)
-        ops.pixel_shuffle_ln(vit_w.h, v['mlp1.m0w'], v['mlp1.m0b'], ps_ln, T, G_, C1, 1e-5, 1 if cfg.ps_version == 'v1' else 0)
-        ops.gemm(L.EPI_BIAS_GELU, ps_ln, v['mlp1.m1w'], out=g1, bias=v['mlp1.m1b'], aux_out=z1, ld_aux=z1.stride(0))      # g1 + the pre-activation z1 (GELU backward)
-        ops.gemm(L.EPI_BIAS, g1, v['mlp1.m3w'], out=feat, bias=v['mlp1.m3b'])
+        backward.projector_forward(vit_w.h, v, ps_raw, ps_ln, z1, g1, feat, T, G_, C1, 1 if cfg.ps_version == 'v1' else 0)
         if image_flags is not None:
             keep = self._h2d((image_flags.detach().to('cpu').reshape(-1) == 1).nonzero().flatten())          # indices of the real tiles
             feat_used = feat.view(T, cfg.num_image_token, H).index_select(0, keep).reshape(-1, H)
@@ -628,13 +537,13 @@ class SFTModel:
         # does: one launch less per layer (`VLASER_SFT_NO_SEAM_NORM=1`: A/B)
         seam = os.environ.get('VLASER_SFT_NO_SEAM_NORM') != '1'
         xn = self.xn[:S]
-        bucket_of = lambda li: 1 + (Lyr - 1 - li) // self.bucket_layers          # layer buckets hold the layers in reverse order (bucket 1 = last layers)
+        bucket_of = self.bucket_of_layer
         x1_ready = False
         for i in range(Lyr):
-            self._wait_params(bucket_of(i))
+            self._wait_params(bucket_of[i])
             _, _, h2, _, _, _, act = self._layer_forward(i, self.h_in[i, :S], S, pos, x1_ready=x1_ready)
             # (only inside a parameter bucket: across a boundary the seam would have to wait for the NEXT bucket's AdamW / all-gather one GEMM early)
-            x1_ready = seam and i + 1 < Lyr and bucket_of(i + 1) == bucket_of(i)
+            x1_ready = seam and i + 1 < Lyr and bucket_of[i + 1] == bucket_of[i]
             if x1_ready:
                 self._layer_out(i, S, h2, act, self.h_in[i + 1, :S], norm_w=v[f'l{i + 1}.ln_in'], x_out=self._saved(i + 1, S)[0])
             else:
@@ -649,7 +558,7 @@ class SFTModel:
             # rank (one reduce-scatter per bucket, in backward order)
             self.fp.g.zero_()
             self._embed_touched = None
-            if getattr(self, '_fused_norm', False):
+            if self._fused_norm:
                 self.norm_parts.zero_()            # nothing wrote this step's slots: the producers' partial sums of the PREVIOUS step must not become this step's norm
             if on_bucket_ready:
                 for b in range(len(self.buckets)):
@@ -680,7 +589,7 @@ class SFTModel:
             ops.gemm_nn(L.EPI_PARTIAL, dlog, self.head_full, out_f32=part, k_splits=sp)
             ops.reduce_norm(None, part, sp, R, H, dx_rows)          # fp32 sum of the slabs in slab order, one rounding to bf16
         else:
-            self._dgrad(dlog, self.head_full, dx_rows, R)
+            backward.dgrad_nn(dlog, self.head_full, dx_rows, self.part)
         ops.gemm_tn(dlog_pad[:, :V], x_pad, gv['head'], sumsq_part=self._ssq('head'))             # dW_head = dlogits^T @ x over ceil64(R) rows (zero pad rows; dlogits rows are padded to Vp columns)
         dxn = self.dx[:S]
         dxn.zero_()
@@ -693,10 +602,6 @@ class SFTModel:
         G = nq // nkv
         sm = self.cache.s_max
         scale = hd ** -0.5
-        bucket_of_layer = {}
-        layers_rev = list(reversed(range(Lyr)))
-        for j, li in enumerate(layers_rev):
-            bucket_of_layer[li] = 1 + j // self.bucket_layers
         nslot = 0                       # norm-weight gradients of the current bucket whose partials wait in self.normw_multi
         for i in reversed(range(Lyr)):
             h_in = self.h_in[i, :S]
@@ -710,10 +615,10 @@ class SFTModel:
                 # (the stand-alone pass read d(act) and the pre-activations back and wrote 2 I columns per row)
                 ops.gemm_nn(L.EPI_SWIGLU_BWD, dh, v[f'l{i}.wdown'], out=dgu, res=gu)
             else:
-                self._dgrad(dh, v[f'l{i}.wdown'], dact, S)
+                backward.dgrad_nn(dh, v[f'l{i}.wdown'], dact, self.part)
                 ops.swiglu_bwd(gu, dact, dgu, S, I)
             ev_wdown = self._wgrad_side(dh, act, gv[f'l{i}.wdown'], S, padded=True, ssq=self._ssq(f'l{i}.wdown'), want_done=True)
-            slabs = self._dgrad(dgu, v[f'l{i}.wgu'], dx, S, keep_slabs=self._slab_norm)
+            slabs = backward.dgrad_nn(dgu, v[f'l{i}.wgu'], dx, self.part, keep_slabs=self._slab_norm)
             self._wgrad_side(dgu, x2, gv[f'l{i}.wgu'], S, padded=True, ssq=self._ssq(f'l{i}.wgu'))
             nw = self.normw_multi
             dw_kw = dict(dw_out=gv[f'l{i}.ln_post'], dw_ws=self.normw_ws) if nw is None else dict(dw_ws=nw[nslot * self.normw_slot:(nslot + 1) * self.normw_slot])
@@ -723,7 +628,7 @@ class SFTModel:
                 ops.rmsnorm_bwd(dx, h2, v[f'l{i}.ln_post'], dh, dh2, S, H, llm.rms_norm_eps, **dw_kw)
             nslot += nw is not None
             # attention block: h2 = h_in + ao Wo^T
-            self._dgrad(dh2, v[f'l{i}.wo'], dao, S)
+            backward.dgrad_nn(dh2, v[f'l{i}.wo'], dao, self.part)
             self._wgrad_side(dh2, ao, gv[f'l{i}.wo'], S, padded=True, ssq=self._ssq(f'l{i}.wo'))
             Kc, VTc = self.cache.k[kslot, 0], self.cache.vt[kslot, 0]         # [nkv, s_max, hd], [nkv, hd, s_max]
             if self.attn_bwd_mode == 'fused':
@@ -732,14 +637,14 @@ class SFTModel:
                 self._attn_backward(q, Kc, VTc, dao, ao, S, nq, G, hd, sm, scale)
             dqkv = self.dqkv[:S]
             ops.rope_bwd_pack(self.dq[:S], self.dk[:S], self.dv[:S], self.rope[0], self.rope[1], pos, dqkv, S, nq, nkv, kv_per_q_head=True)
-            self._dgrad(dqkv, v[f'l{i}.wqkv'], dx, S)
+            backward.dgrad_nn(dqkv, v[f'l{i}.wqkv'], dx, self.part)
             self._wgrad_side(dqkv, x1, gv[f'l{i}.wqkv'], S, bias_out=gv[f'l{i}.bqkv'], padded=True, ssq=self._ssq(f'l{i}.wqkv'))
             if ev_wdown is not None:
                 torch.cuda.current_stream().wait_event(ev_wdown)          # the down_proj weight gradient read dh, which the next kernel overwrites
             dw_kw = dict(dw_out=gv[f'l{i}.ln_in'], dw_ws=self.normw_ws) if nw is None else dict(dw_ws=nw[nslot * self.normw_slot:(nslot + 1) * self.normw_slot])
             ops.rmsnorm_bwd(dx, h_in, v[f'l{i}.ln_in'], dh2, dh, S, H, llm.rms_norm_eps, **dw_kw)
             nslot += nw is not None
-            last_of_bucket = i == 0 or bucket_of_layer[i - 1] != bucket_of_layer[i]
+            last_of_bucket = i == 0 or bucket_of[i - 1] != bucket_of[i]
             if nw is not None and last_of_bucket:
                 # the bucket's layers are i .. i + nslot/2 - 1, visited last to first: slots = (ln_post, ln_in) of layer i + nslot/2 - 1, ..., of layer i
                 key = (i, nslot)
@@ -752,7 +657,7 @@ class SFTModel:
                 nslot = 0
             if on_bucket_ready and last_of_bucket:
                 self._join_wgrad()
-                on_bucket_ready(bucket_of_layer[i])
+                on_bucket_ready(bucket_of[i])
         self._join_wgrad()
         # ---- embeddings (text rows) and projector (image rows)
         ops.embed_scatter_add(ids, self.rank_ws, dh, gv['embed'], S, H, sumsq_part=self._ssq('embed'))
@@ -764,17 +669,7 @@ class SFTModel:
             dvit.view(T, cfg.num_image_token, H).index_copy_(0, keep, dfeat_used.view(-1, cfg.num_image_token, H))
         else:
             dvit.copy_(dfeat_used)
-        dg1, dz1, dln = self.dg1[:nt], self.dz1[:nt], self.dln[:nt]
-        ops.gemm_nn(L.EPI_NONE, dvit, v['mlp1.m3w'], out=dg1)
-        self._wgrad(dvit, g1, gv['mlp1.m3w'], nt, bias_out=gv['mlp1.m3b'])
-        ops.gelu_bwd(z1, dg1, dz1)
-        self._wgrad(dz1, ps_ln, gv['mlp1.m1w'], nt, bias_out=gv['mlp1.m1b'])
-        ops.gemm_nn(L.EPI_NONE, dz1, v['mlp1.m1w'], out=dln)
-        C4 = C1 * 4
-        ops.colsum_mul(dln, ps_raw, self.col, nt, C4, 3, 1e-5, self.rowstat)
-        gv['mlp1.m0w'].copy_(self.col[:C4])
-        ops.colsum_mul(dln, None, self.col, nt, C4, 0, ws=self.rowstat)
-        gv['mlp1.m0b'].copy_(self.col[:C4])
+        backward.projector_backward(dvit, v, gv, ps_raw, ps_ln, z1, g1, self.dg1[:nt], self.dz1[:nt], self.dln[:nt], self.col, self.rowstat)
         if on_bucket_ready:
             on_bucket_ready(len(self.buckets) - 1)
         return loss
@@ -795,17 +690,7 @@ class SFTModel:
             n = nq * nb * kp
             sc, dP = self.sc.view(-1)[:n].view(nq, nb, kp), self.dP.view(-1)[:n].view(nq, nb, kp)
             P, dS = self.P.view(-1)[:n].view(nq, nb, kp), self.dS.view(-1)[:n].view(nq, nb, kp)
-            ops.gemm_raw(L.EPI_F32, q[q0:], Kc, sc, nb, q1, hd, nq * hd, hd, kp, batch=nq, a_bs=hd, w_bs=sm * hd, o_bs=nb * kp, w_group=G)     # Q K^T
-            # dP = dO V^T and (below) dQ = dS K in the NN form: V^T [hd, keys] and K [keys, hd] are read as the cache holds them (r01/r02
-            # transposed both per layer); dS is zero beyond the causal range, so cache rows past S only need to be finite
-            ops.gemm_raw_nn(L.EPI_F32, dao[q0:], VTc, dP, nb, kp, hd, nq * hd, sm, kp, batch=nq, a_bs=hd, w_bs=hd * sm, o_bs=nb * kp, w_group=G)   # dO V^T
-            ops.attn_bwd_pds_masked(sc, dP, dao[q0:], ao[q0:], P, dS, nq, nb, kp, hd, scale, True, kp, q0)      # P = softmax(S), dS = P o (dP - D) * scale
-            ops.gemm_raw_nn(L.EPI_NONE, dS, Kc, self.dq[q0:], nb, hd, kp, kp, hd, nq * hd, batch=nq, a_bs=nb * kp, w_bs=sm * hd, o_bs=hd, w_group=G)  # dQ = dS K
-            # dK[kvh] = sum_g dS[kvh*G+g]^T Q_g, dV[kvh] = sum_g P[kvh*G+g]^T dO_g: contraction along the rows (q) of both operands,
-            # summed over the q heads of the kv group, straight from dS / P [head, q, k] and q / dO [q, head*hd]
-            # one TN GEMM per Q head (108 workgroups instead of 18 serial ones); the sum over the group happens in rope_bwd_pack
-            ops.gemm_tn_grouped(dS, q[q0:], self.dk, q1, hd, nb, kp, nq * hd, nq * hd, 1, 0, 0, nq, nb * kp, hd, hd)
-            ops.gemm_tn_grouped(P, dao[q0:], self.dv, q1, hd, nb, kp, nq * hd, nq * hd, 1, 0, 0, nq, nb * kp, hd, hd)
+            backward.attn_bwd_materialised(q[q0:], Kc, VTc, dao[q0:], ao[q0:], sc, dP, P, dS, self.dq[q0:], self.dk, self.dv, nb, q1, kp, nq, G, hd, sm, scale, True, kp, q0)
             if nblk > 1:
                 last = bi == nblk - 1
                 for g_, acc in ((self.dk, self.dkv_acc[0]), (self.dv, self.dkv_acc[1])):
@@ -819,8 +704,8 @@ class SFTModel:
         """Single rank: bucket b's share of the squared gradient norm as soon as its gradients are complete, on the optimizer stream
         (a one-workgroup-per-CU streaming kernel under the backward's GEMMs) instead of a 0.6 ms pass between backward and AdamW.
         Buckets complete in index order, so the partial sums are added in the same order as the loop in optimizer_step."""
-        self._norm_buckets_seen = getattr(self, '_norm_buckets_seen', 0) + 1
-        if getattr(self, '_fused_norm', False):
+        self._norm_buckets_seen += 1
+        if self._fused_norm:
             # r04: the producers left the partial sums (weight-gradient GEMM epilogues, the touched embedding rows); the small tensors are summed here in
             # one launch, then one workgroup adds the bucket's slots in a fixed order -- on the compute stream: two ~5 us launches per bucket instead of
             # 3.6 GB re-read under the backward's GEMMs.  Every AdamW of the previous step was waited for by the forward, so nothing reads gnorm2 now.
@@ -829,27 +714,24 @@ class SFTModel:
                 ops.sumsq_chunks(self.fp.g, tab, self.norm_parts[c_lo:hi])
             ops.sum_partials(self.norm_parts[lo:hi], self.gnorm2, accumulate=b != 0)
             return
-        ev = torch.cuda.Event()
-        ev.record()
-        with torch.cuda.stream(self.opt_stream):
-            self.opt_stream.wait_event(ev)
+        with behind_current(self.opt_stream):
             if b == 0:
                 self.gnorm2.zero_()          # on this stream: behind the previous step's AdamW, which reads the old norm here
-            s_lo, s_hi, _ = self.shards[b]
-            if s_hi > s_lo:
-                ops.sumsq(self.fp.g[s_lo:s_hi], self.gnorm2, self.sumsq_ws)
+            self.add_sumsq(self.gnorm2, self.sumsq_ws, b)
 
     def _exchange_bucket(self, b):
         """mean reduce-scatter of bucket b on the comm stream (RCCL), issued as soon as its gradients are complete."""
-        if not self.dp_active:
-            return
-        lo, hi = self.buckets[b]
-        s_lo, s_hi, per = self.shards[b]
-        ev = torch.cuda.Event()
-        ev.record()
-        with torch.cuda.stream(self.comm_stream):
-            self.comm_stream.wait_event(ev)
-            dp.reduce_scatter_mean(self.fp.g, self.buckets[b], self.shards[b], self.pg, capi=self.capi)
+        if self.dp_active:
+            self.reduce_scatter_bucket(b, self.comm_stream, self.pg, self.capi)
+
+    def _gather_bucket(self, b):
+        """All-gather of bucket b's updated parameters on the current stream + the event the next forward waits for (`_wait_params`)."""
+        self.all_gather_bucket(b, self.pg, self.capi)
+        self._mark_params(b)
+
+    def _mark_params(self, b):
+        self.ag_events[b] = torch.cuda.Event()
+        self.ag_events[b].record()
 
     def optimizer_step(self, lr=None):
         with self._on_main():
@@ -861,14 +743,12 @@ class SFTModel:
         if self.dp_active:
             torch.cuda.current_stream().wait_stream(self.comm_stream)
         # global gradient norm over the (reduced) shards -> clip factor
-        if getattr(self, '_norm_early', False):
+        if self._norm_early:
             torch.cuda.current_stream().wait_stream(self.opt_stream)     # the per-bucket sums queued from the backward (`_norm_bucket`)
             self._norm_early = False
         else:
             self.gnorm2.zero_()
-            for (s_lo, s_hi, _) in self.shards:
-                if s_hi > s_lo:
-                    ops.sumsq(self.fp.g[s_lo:s_hi], self.gnorm2, self.sumsq_ws)
+            self.add_sumsq(self.gnorm2, self.sumsq_ws)
         if self.capi is not None:                                  # the 4-byte sum on the package's own communicator / stream too
             self.comm_stream.wait_stream(torch.cuda.current_stream())
             self.capi.all_reduce_sum(self.gnorm2)
@@ -877,69 +757,44 @@ class SFTModel:
             torch.distributed.all_reduce(self.gnorm2, group=self.pg)
         gnorm = self.gnorm2.sqrt()                                  # device tensor: reading it is the caller's (only) sync
 
-        def adamw_bucket(b):
-            (s_lo, s_hi, per), o = self.shards[b], self.shard_off[b]
-            if s_hi > s_lo:
-                n = s_hi - s_lo
-                # clip factor max_norm / (||g|| + 1e-6) resolved inside the kernel from the device-resident squared norm
-                ops.adamw_clipped(self.fp.p[s_lo:s_hi], self.master[o:o + n], self.m[o:o + n], self.v[o:o + n], self.fp.g[s_lo:s_hi], lr, self.betas[0],
-                                  self.betas[1], self.eps, self.wd, 1.0, self.gnorm2, self.max_grad_norm, self.step_count)
+        def adamw(b):
+            self.adamw_bucket(b, lr, self.betas, self.eps, self.wd, self.gnorm2, self.max_grad_norm, self.step_count)
 
         if not self.dp_active and self.overlap_optimizer:
             # pipelined with the NEXT step: bucket by bucket on `opt_stream`, embed + projector first, lm_head last; the next forward
             # waits per bucket (`_wait_params`); by the time its backward starts every bucket has been waited for.  The
             # update is therefore still in flight when this returns: `wait_optimizer()` before touching parameter buffers directly.
-            ev = torch.cuda.Event()
-            ev.record()
-            with torch.cuda.stream(self.opt_stream):
-                self.opt_stream.wait_event(ev)
+            with behind_current(self.opt_stream):
                 for b in reversed(range(len(self.buckets))):
-                    adamw_bucket(b)
-                    self.ag_events[b] = torch.cuda.Event()
-                    self.ag_events[b].record()
+                    adamw(b)
+                    self._mark_params(b)
             return gnorm
         if self.dp_active and self.overlap_allgather and os.environ.get('VLASER_SFT_DP_SERIAL_ADAMW') != '1':
             # ZeRO-1 (r03): this rank's shard of every bucket is updated ON THE COMM STREAM right in front of that bucket's parameter all-gather, bucket by
             # bucket in the order the NEXT forward consumes them (embed + projector first, lm_head last); the forward waits per bucket (`_wait_params`), so
             # AdamW (1/N of the parameters) and the exchange both run under the frozen ViT and the earlier layers instead of between two steps
             # (world 1 with the exchange forced on: 31.0 -> 28.9 ms per step, profiles/r03dp_force_dp_world1.md)
-            ev = torch.cuda.Event()
-            ev.record()
             if self.main_stream is not None:
                 # capi mode with CU masks: the comm stream owns only RCCL's share of the CUs -- the shard AdamW (HBM-bound) runs on the compute-masked optimizer stream,
                 # bucket by bucket, and each bucket's all-gather follows it on the comm stream behind an event
-                self.opt_stream.wait_event(ev)
-                for b in reversed(range(len(self.buckets))):
-                    with torch.cuda.stream(self.opt_stream):
-                        adamw_bucket(b)
-                        eb = torch.cuda.Event()
-                        eb.record()
-                    with torch.cuda.stream(self.comm_stream):
-                        self.comm_stream.wait_event(eb)
-                        dp.all_gather_params(self.fp.p, self.buckets[b], self.shards[b], self.pg, capi=self.capi)
-                        self.ag_events[b] = torch.cuda.Event()
-                        self.ag_events[b].record()
+                with behind_current(self.opt_stream):
+                    for b in reversed(range(len(self.buckets))):
+                        adamw(b)
+                        with behind_current(self.comm_stream):
+                            self._gather_bucket(b)
                 return gnorm
-            with torch.cuda.stream(self.comm_stream):
-                self.comm_stream.wait_event(ev)
+            with behind_current(self.comm_stream):
                 for b in reversed(range(len(self.buckets))):
-                    adamw_bucket(b)
-                    dp.all_gather_params(self.fp.p, self.buckets[b], self.shards[b], self.pg, capi=self.capi)
-                    self.ag_events[b] = torch.cuda.Event()
-                    self.ag_events[b].record()
+                    adamw(b)
+                    self._gather_bucket(b)
             return gnorm
         for b in range(len(self.buckets)):
-            adamw_bucket(b)
+            adamw(b)
         if self.dp_active:
             # all-gather the updated bf16 parameters bucket by bucket on the comm stream, in the order the NEXT forward consumes them
-            ev = torch.cuda.Event()
-            ev.record()
-            with torch.cuda.stream(self.comm_stream):
-                self.comm_stream.wait_event(ev)
+            with behind_current(self.comm_stream):
                 for b in reversed(range(len(self.buckets))):
-                    dp.all_gather_params(self.fp.p, self.buckets[b], self.shards[b], self.pg, capi=self.capi)
-                    self.ag_events[b] = torch.cuda.Event()
-                    self.ag_events[b].record()
+                    self._gather_bucket(b)
             if not self.overlap_allgather:
                 torch.cuda.current_stream().wait_stream(self.comm_stream)
         return gnorm
@@ -988,8 +843,7 @@ class SFTModel:
         """Sample-wise gradient accumulation, bucket by bucket as the backward completes them: acc (fp32) += w * g; on the LAST sample
         the bucket is rounded back to bf16 and handed to the exchange (one reduce-scatter per bucket per step, like DDP's no_sync /
         DeepSpeed's gradient-accumulation boundary: train.py:470-482, zero_stage1_config.json)."""
-        lo, hi = self.buckets[b]
-        ops.grad_accumulate(self.fp.g[lo:hi], self.gacc[lo:hi], w, first, last)
+        self.accumulate_bucket(b, w, first, last)
         self._embed_touched = None              # (the finalised bucket holds every sample's rows: the next call clears the whole table)
         if last:
             self._exchange_bucket(b)
@@ -1030,7 +884,7 @@ class SFTModel:
             # ... and a slot layout that depends on the weight's shape only: true for the LDS-DMA weight-gradient kernel the step takes by default; the A/B fallback
             # (VLASER_SFT_WGRAD=tn) picks its kernel -- and with it the slots it reaches -- by the sequence length, so it keeps the buffer pass
             self._fused_norm = early and self.wgrad_lds and os.environ.get('VLASER_SFT_NO_FUSED_NORM') != '1'
-            if self._fused_norm and getattr(self, 'norm_parts', None) is None:
+            if self._fused_norm and self.norm_parts is None:
                 self._plan_fused_norm()
             try:
                 loss = self.forward_backward(*work[0][:4], on_bucket_ready=self._norm_bucket if early else self._exchange_bucket)
@@ -1039,8 +893,6 @@ class SFTModel:
             # a forward_backward that raised never gets here, and one that returned must have signalled every bucket
             self._norm_early = early and self._norm_buckets_seen == len(self.buckets)
         else:
-            if self.gacc is None:
-                self.gacc = torch.zeros(self.fp.n, dtype=F32, device=self.device)
             loss = torch.zeros((), device=self.device)
             for j, (pvb, idb, lbb, flb, w) in enumerate(work):
                 first, last = j == 0, j == len(work) - 1
@@ -1107,9 +959,8 @@ class SFTModel:
         if self.rank == 0:
             self.save_pretrained(path)
         self.wait_optimizer()
-        torch.save({'step_count': self.step_count, 'world': self.world, 'rank': self.rank, 'shards': self.shards, 'lr': self.lr, 'betas': self.betas,
-                    'eps': self.eps, 'weight_decay': self.wd, 'master': self.master.cpu(), 'exp_avg': self.m.cpu(), 'exp_avg_sq': self.v.cpu()},
-                   os.path.join(path, f'optimizer_rank{self.rank:05d}_of_{self.world:05d}.pt'))
+        torch.save({'step_count': self.step_count, 'world': self.world, 'rank': self.rank, 'lr': self.lr, 'betas': self.betas, 'eps': self.eps,
+                    'weight_decay': self.wd, **self.optimizer_state()}, os.path.join(path, f'optimizer_rank{self.rank:05d}_of_{self.world:05d}.pt'))
 
     def load_checkpoint(self, path):
         """Weights through `load_hf_checkpoint` (key names unchanged), then this rank's optimizer shard; the bf16 parameters are
@@ -1119,13 +970,8 @@ class SFTModel:
         _, sd = load_hf_checkpoint(path)
         self.load_state_dict(sd)
         st = torch.load(os.path.join(path, f'optimizer_rank{self.rank:05d}_of_{self.world:05d}.pt'), map_location='cpu', weights_only=True)
-        if st['world'] != self.world or [tuple(x) for x in st['shards']] != [tuple(x) for x in self.shards]:
-            raise ValueError(f"optimizer shard was written for world size {st['world']} / another bucket layout")
+        self.load_optimizer_state(st)
         self.step_count = st['step_count']
-        self.master.copy_(st['master']); self.m.copy_(st['exp_avg']); self.v.copy_(st['exp_avg_sq'])
-        for (lo, hi, _), o in zip(self.shards, self.shard_off):
-            if hi > lo:
-                self.fp.p[lo:hi].copy_(self.master[o:o + hi - lo].to(BF))
         return self
 
     def save_pretrained(self, path, max_shard_bytes=4 << 30):
@@ -1137,41 +983,16 @@ class SFTModel:
         save_hf_checkpoint(path, self.cfg, sd, max_shard_bytes)
 
     # ------------------------------------------------------------------ export (HF key names, un-packed layouts)
-    def state_dict(self):
+    def state_dict(self, grads=False):
         self.wait_optimizer()                                              # pending parameter updates / all-gathers
-        llm = self.llm
-        v = self.fp.view
-        nq, nkv, hd = llm.num_attention_heads, llm.num_key_value_heads, llm.head_dim
-        inv = torch.empty(hd, dtype=torch.long)
-        inv[ops.head_perm(hd)] = torch.arange(hd)
+        v = self.fp.gview if grads else self.fp.view
         out = {'language_model.lm_head.weight': v['head'].clone(), 'language_model.model.norm.weight': v['norm'].clone(),
                'language_model.model.embed_tokens.weight': v['embed'].clone()}
-        for i in range(llm.num_hidden_layers):
-            p = f'language_model.model.layers.{i}.'
-            w, b = v[f'l{i}.wqkv'], v[f'l{i}.bqkv']
-            nh = nq + 2 * nkv
-            idx = (torch.arange(nh)[:, None] * hd + inv[None, :]).reshape(-1).to(w.device)
-            wn, bn = w[idx], b[idx]              # natural row order: packed[head*128 + inv[d]] = natural[head*128 + d]
-            out[p + 'self_attn.q_proj.weight'], out[p + 'self_attn.q_proj.bias'] = wn[:nq * hd].clone(), bn[:nq * hd].clone()
-            out[p + 'self_attn.k_proj.weight'], out[p + 'self_attn.k_proj.bias'] = wn[nq * hd:(nq + nkv) * hd].clone(), bn[nq * hd:(nq + nkv) * hd].clone()
-            out[p + 'self_attn.v_proj.weight'], out[p + 'self_attn.v_proj.bias'] = wn[(nq + nkv) * hd:].clone(), bn[(nq + nkv) * hd:].clone()
-            out[p + 'self_attn.o_proj.weight'] = v[f'l{i}.wo'].clone()
-            gu = v[f'l{i}.wgu'].view(-1, 2, 16, llm.hidden_size)
-            out[p + 'mlp.gate_proj.weight'] = gu[:, 0].reshape(-1, llm.hidden_size).clone()
-            out[p + 'mlp.up_proj.weight'] = gu[:, 1].reshape(-1, llm.hidden_size).clone()
-            out[p + 'mlp.down_proj.weight'] = v[f'l{i}.wdown'].clone()
-            out[p + 'input_layernorm.weight'] = v[f'l{i}.ln_in'].clone()
-            out[p + 'post_attention_layernorm.weight'] = v[f'l{i}.ln_post'].clone()
-        for nm, k in [('m0w', 'mlp1.0.weight'), ('m0b', 'mlp1.0.bias'), ('m1w', 'mlp1.1.weight'), ('m1b', 'mlp1.1.bias'),
-                      ('m3w', 'mlp1.3.weight'), ('m3b', 'mlp1.3.bias')]:
-            out[k] = v['mlp1.' + nm].clone()
+        for i in range(self.llm.num_hidden_layers):
+            out.update(unpack_decoder_layer(v, f'l{i}.', f'language_model.model.layers.{i}.', self.llm))
+        out.update(unpack_mlp1(v))
         return out
 
     def named_grads(self):
         """Gradients under HF key names (un-packed), for parity tests."""
-        saved = self.fp.view
-        self.fp.view = self.fp.gview
-        try:
-            return self.state_dict()
-        finally:
-            self.fp.view = saved
+        return self.state_dict(grads=True)

@@ -26,11 +26,11 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib as L
-from . import dp, ops, prep
+from . import ops, prep
 from .config import VLAConfig
 from .engine import BF, KVCache, PrefillBuffers, QwenStack, VitEngine, prefill_begin, prefill_layer
 from .pizero import canonicalize_vla_state_dict, stage_pixels
-from .sft import FlatParams
+from .param_group import FlatParams, ParamGroup, decoder_layer_specs, pack_decoder_layer, unpack_decoder_layer
 
 F32 = torch.float32
 
@@ -73,18 +73,15 @@ class ModelAveraging:
         self.trainer, self.use_ema, self.use_swa = trainer, use_ema, use_swa
         self.ema_start, self.ema_decay, self.ema_freq = ema_start, ema_decay, ema_freq
         self.swa_start, self.swa_freq = swa_start, swa_freq
-        self.avg = None
+        self.avg = None               # of the action expert's masters
         self.avg_vlm = None           # train_vlm=True: the reference's AveragedModel wraps the WHOLE PiZero, so the VLM group is averaged too
         self.n_averaged = 0
 
     def _groups(self):
-        """(flat parameter owner, its average) per trained group: the action expert and, with `train_vlm`, the VLM group (vision tower, projector, VLM
+        """(parameter group, its average) per trained group: the action expert and, with `train_vlm`, the VLM group (vision tower, projector, VLM
         decoder layers) -- `AveragedModel(model)` (model_averaging.py:33-44) averages every parameter of the model it wraps."""
         tr = self.trainer
-        out = [(tr, self.avg)]
-        if getattr(tr, 'vg', None) is not None:
-            out.append((tr.vg, self.avg_vlm))
-        return out
+        return list(zip([tr] if getattr(tr, 'vg', None) is None else [tr, tr.vg], (self.avg, self.avg_vlm)))
 
     def maybe_initialize(self, cnt_update):
         if (self.use_swa and cnt_update == self.swa_start) or (self.use_ema and cnt_update == self.ema_start):
@@ -112,12 +109,10 @@ class ModelAveraging:
         keep = [owner.fp.p.clone() for owner, _ in groups]
         try:
             for owner, avg in groups:
-                for (lo, hi, _), o in zip(owner.shards, owner.shard_off):
-                    if hi > lo:
-                        owner.fp.p[lo:hi].copy_(avg[o:o + hi - lo].to(BF))
+                owner.params_from(avg)
                 if tr.dp_active:
                     for b in range(len(owner.buckets)):
-                        dp.all_gather_params(owner.fp.p, owner.buckets[b], owner.shards[b], tr.pg)
+                        owner.all_gather_bucket(b, tr.pg)
             sd = tr.state_dict()
         finally:
             for (owner, _), k in zip(groups, keep):
@@ -125,7 +120,7 @@ class ModelAveraging:
         return {'state_dict': sd, 'n_averaged': self.n_averaged, 'model_type': 'ema' if self.use_ema else 'swa'}
 
 
-class VLATrainer:
+class VLATrainer(ParamGroup):
     """`step(batch...)` = one optimizer update of the action expert on flow-matching samples (per-device batch B >= 1, sample by sample)."""
 
     def __init__(self, cfg: VLAConfig, device='cuda', lr=5e-5, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
@@ -155,13 +150,11 @@ class VLATrainer:
         base, llm = cfg.base, cfg.base.llm
         self.vit = VitEngine(sd, base, dev, max_tiles=1)
         self.vlm = QwenStack(sd, 'language_model.', llm, dev, with_embed=True, with_head=False, gemm=True, skinny=False)      # frozen
-        H, I = ex.hidden_size, ex.intermediate_size
-        nq, nkv, hd = ex.num_attention_heads, ex.num_key_value_heads, ex.head_dim
-        NQ, A, P = (nq + 2 * nkv) * hd, cfg.action_dim, cfg.proprio_dim
+        H, A, P = ex.hidden_size, cfg.action_dim, cfg.proprio_dim
         self.A8 = 8                                 # tiny operands are padded to the kernels' 8-column granularity
         fp = FlatParams(dev)
         fp.add('dec.w', (A, H)); fp.add('dec.b', (A,)); fp.add('norm', (H,))
-        names = [('wqkv', (NQ, H)), ('bqkv', (NQ,)), ('wo', (H, nq * hd)), ('wgu', (2 * I, H)), ('wdown', (H, I)), ('ln_in', (H,)), ('ln_post', (H,))]
+        names = decoder_layer_specs(ex)
         Lyr = ex.num_hidden_layers
         bounds = []
         for j, i in enumerate(reversed(range(Lyr))):
@@ -174,42 +167,20 @@ class VLATrainer:
                         ('pe.b', (H,))]:
             fp.add(nm, shp)
         fp.finalize(pad_to=128 * self.world * 8)
-        self.fp = fp
         g = lambda k: sd[k].to(device=dev, dtype=BF)
         v = fp.view
         v['dec.w'].copy_(g('action_decoder.weight')); v['dec.b'].copy_(g('action_decoder.bias')); v['norm'].copy_(g('action_expert.model.norm.weight'))
         for i in range(Lyr):
-            p = f'action_expert.model.layers.{i}.'
-            wqkv, bqkv = ops.pack_qkv(g(p + 'self_attn.q_proj.weight'), g(p + 'self_attn.k_proj.weight'), g(p + 'self_attn.v_proj.weight'),
-                                      g(p + 'self_attn.q_proj.bias'), g(p + 'self_attn.k_proj.bias'), g(p + 'self_attn.v_proj.bias'), hd)
-            v[f'l{i}.wqkv'].copy_(wqkv); v[f'l{i}.bqkv'].copy_(bqkv)
-            v[f'l{i}.wo'].copy_(g(p + 'self_attn.o_proj.weight'))
-            v[f'l{i}.wgu'].copy_(ops.pack_gate_up(g(p + 'mlp.gate_proj.weight'), g(p + 'mlp.up_proj.weight')))
-            v[f'l{i}.wdown'].copy_(g(p + 'mlp.down_proj.weight'))
-            v[f'l{i}.ln_in'].copy_(g(p + 'input_layernorm.weight')); v[f'l{i}.ln_post'].copy_(g(p + 'post_attention_layernorm.weight'))
+            pack_decoder_layer(sd, f'action_expert.model.layers.{i}.', v, f'l{i}.', ex.head_dim)
         for nm, k in [('ae1', 'action_encoder.linear_1'), ('ae2', 'action_encoder.linear_2'), ('ae3', 'action_encoder.linear_3'), ('pe', 'proprio_encoder')]:
             v[nm + '.w'].copy_(g(k + '.weight')); v[nm + '.b'].copy_(g(k + '.bias'))
-        self.buckets, lo = [], 0
-        for hi in bounds + [fp.n]:
-            if hi > lo:
-                self.buckets.append((lo, hi)); lo = hi
-        assert all((hi - lo) % (128 * self.world) == 0 for lo, hi in self.buckets)
+        self.init_group(fp, bounds + [fp.n], self.world, self.rank)
         self.bucket_of_layer = {i: min(j // self.bucket_layers, len(self.buckets) - 2) for j, i in enumerate(reversed(range(Lyr)))}
-        self.shards = dp.plan_shards(self.buckets, self.world, self.rank)
-        n_shard = sum(hi - lo for lo, hi, _ in self.shards)
-        self.master = torch.zeros(n_shard, dtype=F32, device=dev)
-        self.m = torch.zeros(n_shard, dtype=F32, device=dev)
-        self.v = torch.zeros(n_shard, dtype=F32, device=dev)
-        self.shard_off, o = [], 0
-        for lo, hi, _ in self.shards:
-            self.master[o:o + hi - lo].copy_(fp.p[lo:hi].float())
-            self.shard_off.append(o); o += hi - lo
         self._alloc()
         self._refresh_transposes()
         if self.train_vlm:
             from .vla_vlm_group import VLMGroup
             self.vg = VLMGroup(self, sd, self.bucket_layers)
-            self.gacc_v = None
         return self
 
     def _alloc(self):
@@ -251,7 +222,6 @@ class VLATrainer:
         self.normw_ws = torch.zeros(8 * H, dtype=F32, device=dev)
         self.gnorm2 = torch.zeros(1, dtype=F32, device=dev)
         self.sumsq_ws = torch.zeros(1024, dtype=F32, device=dev)
-        self.gacc = None
         self.comm_stream = torch.cuda.Stream(device=dev) if self.dp_active else None
 
     def _refresh_transposes(self):
@@ -281,7 +251,7 @@ class VLATrainer:
         if bias_out is not None:
             ops.colsum_bf16(dY[:M], bias_out, M, dY.shape[1])
 
-    def _linear(self, x, w, b, out, M, gelu=False):
+    def _linear(self, x, w, b, out, M):
         ops.gemm(L.EPI_BIAS, x[:M], w, out=out[:M], bias=b)
 
     # ------------------------------------------------------------------ forward + backward of ONE sample
@@ -431,61 +401,48 @@ class VLATrainer:
             self.vg.backward_tail(ids_h)                # mlp1, pixel_shuffle, the vision tower and its embeddings
         return loss
 
-    # ------------------------------------------------------------------ optimizer / data parallel (same machinery as the SFT step)
-    def _exchange_bucket(self, b):
-        if not self.dp_active:
-            return
-        ev = torch.cuda.Event(); ev.record()
-        with torch.cuda.stream(self.comm_stream):
-            self.comm_stream.wait_event(ev)
-            dp.reduce_scatter_mean(self.fp.g, self.buckets[b], self.shards[b], self.pg)
+    # ------------------------------------------------------------------ optimizer / data parallel (the groups' per-bucket operations: param_group.py)
+    def groups(self):
+        """The trained parameter groups: the action expert (this object) and, with `train_vlm`, the VLM group."""
+        return [self] if self.vg is None else [self, self.vg]
+
+    def _exchange_bucket(self, b, group=None):
+        if self.dp_active:
+            (self if group is None else group).reduce_scatter_bucket(b, self.comm_stream, self.pg)
 
     def _accumulate_bucket(self, b, w, first, last):
-        lo, hi = self.buckets[b]
-        ops.grad_accumulate(self.fp.g[lo:hi], self.gacc[lo:hi], w, first, last)
+        self.accumulate_bucket(b, w, first, last)
         if last:
             self._exchange_bucket(b)
 
     def _vlm_grads_ready(self, w, first, last, accumulate):
         """VLM group after one sample's backward: accumulate (fp32) when the step has several samples, and hand every bucket to the exchange after
         the last one (no overlap with the backward here: the vision tower finishes last and owns most of the group's buckets anyway)."""
-        vg = self.vg
-        for b, (lo, hi) in enumerate(vg.buckets):
+        for b in range(len(self.vg.buckets)):
             if accumulate:
-                ops.grad_accumulate(vg.fp.g[lo:hi], self.gacc_v[lo:hi], w, first, last)
-            if last and self.dp_active:
-                ev = torch.cuda.Event(); ev.record()
-                with torch.cuda.stream(self.comm_stream):
-                    self.comm_stream.wait_event(ev)
-                    dp.reduce_scatter_mean(vg.fp.g, vg.buckets[b], vg.shards[b], self.pg)
+                self.vg.accumulate_bucket(b, w, first, last)
+            if last:
+                self._exchange_bucket(b, self.vg)
 
     def optimizer_step(self, lr=None, vlm_lr=None):
         """clip_grad_norm_ over BOTH groups (train.py:504-507), then one AdamW per group with its own learning rate / weight decay (:509-520)."""
-        lr = self.lr if lr is None else lr
         self.step_count += 1
         if self.dp_active:
             torch.cuda.current_stream().wait_stream(self.comm_stream)
-        groups = [(self.fp, self.shards, self.shard_off, self.master, self.m, self.v, lr, self.wd, self.buckets)]
-        if self.vg is not None:
-            vg = self.vg
-            groups.append((vg.fp, vg.shards, vg.shard_off, vg.master, vg.m, vg.v, self.vlm_lr if vlm_lr is None else vlm_lr, self.vlm_wd, vg.buckets))
+        groups = self.groups()
         self.gnorm2.zero_()
-        for fp, shards, _, _, _, _, _, _, _ in groups:
-            for (s_lo, s_hi, _) in shards:
-                if s_hi > s_lo:
-                    ops.sumsq(fp.g[s_lo:s_hi], self.gnorm2, self.sumsq_ws)
+        for g in groups:
+            g.add_sumsq(self.gnorm2, self.sumsq_ws)
         if self.dp_active:
             torch.distributed.all_reduce(self.gnorm2, group=self.pg)
-        for fp, shards, offs, master, m, v_, glr, gwd, _ in groups:
-            for (s_lo, s_hi, _), o in zip(shards, offs):
-                if s_hi > s_lo:
-                    n = s_hi - s_lo
-                    ops.adamw_clipped(fp.p[s_lo:s_hi], master[o:o + n], m[o:o + n], v_[o:o + n], fp.g[s_lo:s_hi], glr, self.betas[0],
-                                      self.betas[1], self.eps, gwd, 1.0, self.gnorm2, self.max_grad_norm, self.step_count)
+        rates = [(self.lr if lr is None else lr, self.wd), (self.vlm_lr if vlm_lr is None else vlm_lr, self.vlm_wd)]
+        for g, (glr, gwd) in zip(groups, rates):
+            for b in range(len(g.buckets)):
+                g.adamw_bucket(b, glr, self.betas, self.eps, gwd, self.gnorm2, self.max_grad_norm, self.step_count)
         if self.dp_active:
-            for fp, shards, _, _, _, _, _, _, buckets in groups:
-                for b in range(len(buckets)):
-                    dp.all_gather_params(fp.p, buckets[b], shards[b], self.pg)
+            for g in groups:
+                for b in range(len(g.buckets)):
+                    g.all_gather_bucket(b, self.pg)
         self._refresh_transposes()
         return self.gnorm2.sqrt()
 
@@ -494,10 +451,6 @@ class VLATrainer:
         the per-device batch of every accumulation micro-batch, flattened; each sample weighs 1 / len(samples) (the loss is a batch
         mean, `normalized_loss = loss / grad_accumulation_steps`, train.py:479-498)."""
         n = len(samples)
-        if n > 1 and self.gacc is None:
-            self.gacc = torch.zeros(self.fp.n, dtype=F32, device=self.device)
-        if n > 1 and self.vg is not None and self.gacc_v is None:
-            self.gacc_v = torch.zeros(self.vg.fp.n, dtype=F32, device=self.device)
         loss = torch.zeros((), device=self.device)
         for j, smp in enumerate(samples):
             first, last = j == 0, j == n - 1
@@ -512,26 +465,11 @@ class VLATrainer:
     def state_dict(self, grads=False):
         ex = self.cfg.expert
         v = self.fp.gview if grads else self.fp.view
-        nq, nkv, hd = ex.num_attention_heads, ex.num_key_value_heads, ex.head_dim
-        inv = torch.empty(hd, dtype=torch.long); inv[ops.head_perm(hd)] = torch.arange(hd)
         out = {'action_decoder.weight': v['dec.w'].clone(), 'action_decoder.bias': v['dec.b'].clone(), 'action_expert.model.norm.weight': v['norm'].clone()}
         for nm, k in [('ae1', 'action_encoder.linear_1'), ('ae2', 'action_encoder.linear_2'), ('ae3', 'action_encoder.linear_3'), ('pe', 'proprio_encoder')]:
             out[k + '.weight'], out[k + '.bias'] = v[nm + '.w'].clone(), v[nm + '.b'].clone()
         for i in range(ex.num_hidden_layers):
-            p = f'action_expert.model.layers.{i}.'
-            w, b = v[f'l{i}.wqkv'], v[f'l{i}.bqkv']
-            idx = (torch.arange(nq + 2 * nkv)[:, None] * hd + inv[None, :]).reshape(-1).to(w.device)
-            wn, bn = w[idx], b[idx]
-            out[p + 'self_attn.q_proj.weight'], out[p + 'self_attn.q_proj.bias'] = wn[:nq * hd].clone(), bn[:nq * hd].clone()
-            out[p + 'self_attn.k_proj.weight'], out[p + 'self_attn.k_proj.bias'] = wn[nq * hd:(nq + nkv) * hd].clone(), bn[nq * hd:(nq + nkv) * hd].clone()
-            out[p + 'self_attn.v_proj.weight'], out[p + 'self_attn.v_proj.bias'] = wn[(nq + nkv) * hd:].clone(), bn[(nq + nkv) * hd:].clone()
-            out[p + 'self_attn.o_proj.weight'] = v[f'l{i}.wo'].clone()
-            gu = v[f'l{i}.wgu'].view(-1, 2, 16, ex.hidden_size)
-            out[p + 'mlp.gate_proj.weight'] = gu[:, 0].reshape(-1, ex.hidden_size).clone()
-            out[p + 'mlp.up_proj.weight'] = gu[:, 1].reshape(-1, ex.hidden_size).clone()
-            out[p + 'mlp.down_proj.weight'] = v[f'l{i}.wdown'].clone()
-            out[p + 'input_layernorm.weight'] = v[f'l{i}.ln_in'].clone()
-            out[p + 'post_attention_layernorm.weight'] = v[f'l{i}.ln_post'].clone()
+            out.update(unpack_decoder_layer(v, f'l{i}.', f'action_expert.model.layers.{i}.', ex))
         if self.vg is not None:
             out.update(self.vg.state_dict(grads))
         return out
@@ -558,10 +496,9 @@ class VLATrainer:
             # moments of the ZeRO-1 shard -- not torch.optim state dicts)
             extra = {'action_optimizer': None, 'vlm_optimizer': None, 'action_lr_scheduler': None, 'vlm_lr_scheduler': None, 'wandb_id': None, 'n_averaged': 1}
             save_vla_checkpoint(path, sd, cnt_update=self.step_count, cnt_batch=cnt_batch, extra=extra)
-        st = {'rank': self.rank, 'world': self.world, 'shards': self.shards, 'step_count': self.step_count, 'master': self.master.cpu(),
-              'exp_avg': self.m.cpu(), 'exp_avg_sq': self.v.cpu()}
-        if self.vg is not None:                      # the VLM group's shard of the second optimiser (train_vlm)
-            st.update({'vlm_shards': self.vg.shards, 'vlm_master': self.vg.master.cpu(), 'vlm_exp_avg': self.vg.m.cpu(), 'vlm_exp_avg_sq': self.vg.v.cpu()})
+        st = {'rank': self.rank, 'world': self.world, 'step_count': self.step_count}
+        for g, prefix in zip(self.groups(), ('', 'vlm_')):      # 'vlm_': the VLM group's shard of the second optimiser (train_vlm)
+            st.update(g.optimizer_state(prefix))
         torch.save(st, self._opt_shard_path(path))
 
     def load_checkpoint(self, path, resume_optimizer=True):
@@ -576,21 +513,9 @@ class VLATrainer:
         if not os.path.exists(sp):
             raise FileNotFoundError(f'{sp}: no optimizer shard for rank {self.rank} of {self.world} (resume_optimizer=False loads the weights only)')
         st = torch.load(sp, map_location='cpu', weights_only=True)        # tensors, ints and tuples only
-        if st['world'] != self.world or st['rank'] != self.rank or [tuple(x) for x in st['shards']] != [tuple(x) for x in self.shards]:
-            raise ValueError(f"optimizer shard was written for rank {st['rank']} of {st['world']} / another bucket layout")
+        for g, prefix in zip(self.groups(), ('', 'vlm_')):
+            g.load_optimizer_state(st, prefix)
         self.step_count = st['step_count']
-        self.master.copy_(st['master']); self.m.copy_(st['exp_avg']); self.v.copy_(st['exp_avg_sq'])
-        for (lo, hi, _), o in zip(self.shards, self.shard_off):
-            if hi > lo:
-                self.fp.p[lo:hi].copy_(self.master[o:o + hi - lo].to(BF))
-        if self.vg is not None:
-            vg = self.vg
-            if 'vlm_master' not in st or [tuple(x) for x in st['vlm_shards']] != [tuple(x) for x in vg.shards]:
-                raise ValueError('the optimizer shard holds no (matching) state for the VLM parameter group (train_vlm)')
-            vg.master.copy_(st['vlm_master']); vg.m.copy_(st['vlm_exp_avg']); vg.v.copy_(st['vlm_exp_avg_sq'])
-            for (lo, hi, _), o in zip(vg.shards, vg.shard_off):
-                if hi > lo:
-                    vg.fp.p[lo:hi].copy_(vg.master[o:o + hi - lo].to(BF))
         # (the other ranks' slices of fp.p are the checkpoint's bf16 weights = bf16(their masters): rank 0 saved them after the all-gather)
         self._refresh_transposes()
         return self

@@ -22,14 +22,15 @@ import os
 import torch
 
 from . import _lib as L
-from . import dp, ops
+from . import ops
+from .backward import attn_bwd_materialised, dgrad_nn, projector_backward, projector_forward, wgrad_tn
 from .engine import BF
-from .sft import FlatParams
+from .param_group import DECODER_LAYER_NAMES, MLP1_KEYS, FlatParams, ParamGroup, decoder_layer_specs, mlp1_specs, unpack_decoder_layer, unpack_mlp1
 
 F32 = torch.float32
 
 
-class VLMGroup:
+class VLMGroup(ParamGroup):
     def __init__(self, trainer, sd, bucket_layers=8):
         """`trainer`: the VLATrainer (frozen-prefix engines already built from `sd`); the group re-homes every trained VLM tensor in ONE flat
         bf16 buffer (kernel layouts) and points the engines at views of it, so AdamW updates are what the next forward reads."""
@@ -37,11 +38,8 @@ class VLMGroup:
         cfg, dev = tr.cfg, tr.device
         base, llm, vis = cfg.base, cfg.base.llm, cfg.base.vision
         self.llm, self.vis = llm, vis
-        H, I = llm.hidden_size, llm.intermediate_size
-        nq, nkv, hd = llm.num_attention_heads, llm.num_key_value_heads, llm.head_dim
-        NQ = (nq + 2 * nkv) * hd
-        C, Cm, Hn = vis.hidden_size, vis.intermediate_size, vis.num_attention_heads
-        C4 = 4 * C
+        H = llm.hidden_size
+        C, Cm = vis.hidden_size, vis.intermediate_size
         Lyr, Lv = llm.num_hidden_layers, vis.num_hidden_layers
         world = tr.world
         fp = FlatParams(dev)
@@ -50,10 +48,10 @@ class VLMGroup:
         for j, i in enumerate(reversed(range(Lyr))):
             if j % bucket_layers == 0 and j > 0:
                 fp.align(128 * world); bounds.append(fp.n)
-            for nm, shp in [('wqkv', (NQ, H)), ('bqkv', (NQ,)), ('wo', (H, nq * hd)), ('wgu', (2 * I, H)), ('wdown', (H, I)), ('ln_in', (H,)), ('ln_post', (H,))]:
+            for nm, shp in decoder_layer_specs(llm):
                 fp.add(f'l{i}.{nm}', shp)
         fp.align(128 * world); bounds.append(fp.n)
-        for nm, shp in [('m0w', (C4,)), ('m0b', (C4,)), ('m1w', (H, C4)), ('m1b', (H,)), ('m3w', (H, H)), ('m3b', (H,))]:
+        for nm, shp in mlp1_specs(H, 4 * C):
             fp.add('mlp1.' + nm, shp)
         for j, i in enumerate(reversed(range(Lv))):
             if j % bucket_layers == 0 and j > 0:
@@ -66,15 +64,14 @@ class VLMGroup:
         for nm, shp in [('pe.w', (C, KP)), ('pe.b', (C,)), ('cls', (C,)), ('pos', (vis.num_positions, C))]:
             fp.add('emb.' + nm, shp)
         fp.finalize(pad_to=128 * world * 8)
-        self.fp = fp
         v = fp.view
         # ---- fill from the engines' tensors (already in kernel layout) and re-point the engines at the views
         v['norm'].copy_(tr.vlm.norm); tr.vlm.norm = v['norm']
         for i, lw in enumerate(tr.vlm.layers):
-            for nm in ('wqkv', 'bqkv', 'wo', 'wgu', 'wdown', 'ln_in', 'ln_post'):
+            for nm in DECODER_LAYER_NAMES:
                 v[f'l{i}.{nm}'].copy_(getattr(lw, nm)); setattr(lw, nm, v[f'l{i}.{nm}'])
         vit = tr.vit
-        for nm in ('m0w', 'm0b', 'm1w', 'm1b', 'm3w', 'm3b'):
+        for nm, _ in MLP1_KEYS:
             v['mlp1.' + nm].copy_(getattr(vit, nm)); setattr(vit, nm, v['mlp1.' + nm])
         for i, lw in enumerate(vit.layers):
             for nm in list(lw.keys()):
@@ -83,20 +80,7 @@ class VLMGroup:
         v['emb.pe.b'].copy_(vit.b_pe); vit.b_pe = v['emb.pe.b']
         v['emb.cls'].copy_(vit.cls); vit.cls = v['emb.cls']
         v['emb.pos'].copy_(vit.pos); vit.pos = v['emb.pos']
-        self.buckets, lo = [], 0
-        for hi in bounds + [fp.n]:
-            if hi > lo:
-                self.buckets.append((lo, hi)); lo = hi
-        assert all((hi - lo) % (128 * world) == 0 for lo, hi in self.buckets)
-        self.shards = dp.plan_shards(self.buckets, world, tr.rank)
-        n_shard = sum(hi - lo for lo, hi, _ in self.shards)
-        self.master = torch.zeros(n_shard, dtype=F32, device=dev)
-        self.m = torch.zeros(n_shard, dtype=F32, device=dev)
-        self.v = torch.zeros(n_shard, dtype=F32, device=dev)
-        self.shard_off, o = [], 0
-        for lo, hi, _ in self.shards:
-            self.master[o:o + hi - lo].copy_(fp.p[lo:hi].float())
-            self.shard_off.append(o); o += hi - lo
+        self.init_group(fp, bounds + [fp.n], world, tr.rank)
         self._alloc()
 
     def _alloc(self):
@@ -153,23 +137,6 @@ class VLMGroup:
         self.normw_ws = torch.zeros((T + 3) // 4 * H, dtype=F32, device=dev)
 
     # ------------------------------------------------------------------ helpers
-    def _wgrad(self, dY, X, out, bias_out=None):
-        ops.gemm_tn(dY, X, out)
-        if bias_out is not None:
-            ops.colsum_bf16(dY, bias_out, dY.shape[0], dY.shape[1])
-
-    def _dgrad(self, dY, W, out):
-        """out[S,K] = dY[S,N] @ W[N,K], W as stored; long contractions over few output tiles run split-K (as SFTModel._dgrad)."""
-        S = dY.shape[0]
-        Nin, Kout = W.shape
-        sp = 1 if Nin <= 2048 else ops.gemm_splits(S, Kout, Nin, self.part.numel(), nn=True)
-        if sp > 1:
-            part = self.part[:sp * S * Kout]
-            ops.gemm_nn(L.EPI_PARTIAL, dY, W, out_f32=part, k_splits=sp)
-            ops.reduce_norm(None, part, sp, S, Kout, out)
-        else:
-            ops.gemm_nn(L.EPI_NONE, dY, W, out=out)
-
     def _colsum(self, a, b, out, S, Cc, mode, eps=1e-6):
         ops.colsum_mul(a, b, self.col, S, Cc, mode, eps, self.rowstat)
         out.copy_(self.col[:Cc])
@@ -207,10 +174,7 @@ class VLMGroup:
         # ---- projector (modeling_internvl_chat.py:89-94, 257-291), intermediates kept
         G_ = vis.image_size // vis.patch_size
         v1 = 1 if cfg.base.ps_version == 'v1' else 0
-        ops.pixel_shuffle(self.vh[Lv], self.ps_raw, 1, G_, C, v1)
-        ops.pixel_shuffle_ln(self.vh[Lv], v['mlp1.m0w'], v['mlp1.m0b'], self.ps_ln, 1, G_, C, 1e-5, v1)
-        ops.gemm(L.EPI_BIAS_GELU, self.ps_ln, v['mlp1.m1w'], out=self.g1, bias=v['mlp1.m1b'], aux_out=self.z1, ld_aux=self.z1.stride(0))
-        ops.gemm(L.EPI_BIAS, self.g1, v['mlp1.m3w'], out=self.feat, bias=v['mlp1.m3b'])
+        projector_forward(self.vh[Lv], v, self.ps_raw, self.ps_ln, self.z1, self.g1, self.feat, 1, G_, C, v1)
         # ---- embeddings (pad rows zero: pizero_internvl.py:757-791) and the decoder layers
         h0 = self.h_in[0]
         ops.embed_merge(ids, tr.vlm.embed, self.feat, h0, cfg.base.img_context_token_id, cfg.base.pad_token_id, True, tr.rank_ws)
@@ -264,12 +228,12 @@ class VLMGroup:
         dh, dh2, dx, dao, dqkv = self.dh, self.dh2, self.dx, self.dao, self.dqkv
         if i < Lyr - 1:
             ops.gemm_nn(L.EPI_SWIGLU_BWD, dh, g('wdown'), out=self.dgu, res=self.gu[i])
-            self._wgrad(dh, self.act[i], gg('wdown'))
-            self._dgrad(self.dgu, g('wgu'), dx)
-            self._wgrad(self.dgu, self.x2[i], gg('wgu'))
+            wgrad_tn(dh, self.act[i], gg('wdown'))
+            dgrad_nn(self.dgu, g('wgu'), dx, self.part)
+            wgrad_tn(self.dgu, self.x2[i], gg('wgu'))
             ops.rmsnorm_bwd(dx, self.h2[i], g('ln_post'), dh, dh2, T, H, llm.rms_norm_eps, dw_out=gg('ln_post'), dw_ws=self.normw_ws)
-            self._dgrad(dh2, g('wo'), dao)
-            self._wgrad(dh2, self.ao[i], gg('wo'))
+            dgrad_nn(dh2, g('wo'), dao, self.part)
+            wgrad_tn(dh2, self.ao[i], gg('wo'))
             # attention backward; key k visible iff k < n_valid (bidirectional inside the valid prefix)
             Kc, VTc = tr.cache.k[i, 0], tr.cache.vt[i, 0]
             if self.fused_attn_bwd:
@@ -277,22 +241,11 @@ class VLMGroup:
                 # [heads, T, T] fp32 score matrices: ~200 -> ~40 us per layer (profiles/r06ab_vla_train_kernel_stats.md)
                 ops.attn_bwd(self.q[i], Kc, VTc, self.ao[i], dao, self.lse[i], self.delta_ws, self.dq, self.dk, self.dv, T, nq, nkv, sm, scale, causal=False,
                              kv_valid=n_valid, head_dim=hd)
-                ops.rope_bwd_pack_ex(self.dq, self.dk, self.dv, tr.rope[0], tr.rope[1], tr.pos_vlm, dqkv, T, nq, nkv, kv_per_q_head=True, dk_extra=self.dkx,
-                                     dv_extra=self.dvx)
-                dres = dh2
-                self._dgrad(dqkv, g('wqkv'), dx)
-                self._wgrad(dqkv, self.x1[i], gg('wqkv'), bias_out=gg('bqkv'))
-                ops.rmsnorm_bwd(dx, self.h_in[i], g('ln_in'), dres, dh, T, H, llm.rms_norm_eps, dw_out=gg('ln_in'), dw_ws=self.normw_ws)
-                return
-            n = nq * T * Tp
-            sc, dP = self.sc[:n].view(nq, T, Tp), self.dP[:n].view(nq, T, Tp)
-            P, dS = self.P[:n].view(nq, T, Tp), self.dS[:n].view(nq, T, Tp)
-            ops.gemm_raw(L.EPI_F32, self.q[i], Kc, sc, T, T, hd, nq * hd, hd, Tp, batch=nq, a_bs=hd, w_bs=sm * hd, o_bs=T * Tp, w_group=G)
-            ops.gemm_raw_nn(L.EPI_F32, dao, VTc, dP, T, Tp, hd, nq * hd, sm, Tp, batch=nq, a_bs=hd, w_bs=hd * sm, o_bs=T * Tp, w_group=G)
-            ops.attn_bwd_pds_masked(sc, dP, dao, self.ao[i], P, dS, nq, T, Tp, hd, scale, False, n_valid)
-            ops.gemm_raw_nn(L.EPI_NONE, dS, Kc, self.dq, T, hd, Tp, Tp, hd, nq * hd, batch=nq, a_bs=T * Tp, w_bs=sm * hd, o_bs=hd, w_group=G)
-            ops.gemm_tn_grouped(dS, self.q[i], self.dk, T, hd, T, Tp, nq * hd, nq * hd, 1, 0, 0, nq, T * Tp, hd, hd)
-            ops.gemm_tn_grouped(P, dao, self.dv, T, hd, T, Tp, nq * hd, nq * hd, 1, 0, 0, nq, T * Tp, hd, hd)
+            else:
+                n = nq * T * Tp
+                sc, dP = self.sc[:n].view(nq, T, Tp), self.dP[:n].view(nq, T, Tp)
+                P, dS = self.P[:n].view(nq, T, Tp), self.dS[:n].view(nq, T, Tp)
+                attn_bwd_materialised(self.q[i], Kc, VTc, dao, self.ao[i], sc, dP, P, dS, self.dq, self.dk, self.dv, T, T, Tp, nq, G, hd, sm, scale, False, n_valid)
             ops.rope_bwd_pack_ex(self.dq, self.dk, self.dv, tr.rope[0], tr.rope[1], tr.pos_vlm, dqkv, T, nq, nkv, kv_per_q_head=True, dk_extra=self.dkx,
                                  dv_extra=self.dvx)
             dres = dh2
@@ -301,8 +254,8 @@ class VLMGroup:
             ops.rope_bwd_pack_ex(self.dq, self.zkv, self.zkv, tr.rope[0], tr.rope[1], tr.pos_vlm, dqkv, T, nq, nkv, kv_per_q_head=False, dk_extra=self.dkx,
                                  dv_extra=self.dvx)
             dres = None
-        self._dgrad(dqkv, g('wqkv'), dx)
-        self._wgrad(dqkv, self.x1[i], gg('wqkv'), bias_out=gg('bqkv'))
+        dgrad_nn(dqkv, g('wqkv'), dx, self.part)
+        wgrad_tn(dqkv, self.x1[i], gg('wqkv'), bias_out=gg('bqkv'))
         ops.rmsnorm_bwd(dx, self.h_in[i], g('ln_in'), dres, dh, T, H, llm.rms_norm_eps, dw_out=gg('ln_in'), dw_ws=self.normw_ws)
 
     def backward_tail(self, ids_h):
@@ -317,13 +270,7 @@ class VLMGroup:
         img_rows = (ids_h.reshape(-1) == cfg.base.img_context_token_id).nonzero().flatten().pin_memory().to(tr.device, non_blocking=True)
         self.dfeat.copy_(self.dh.index_select(0, img_rows))                      # index plumbing (the visual-token scatter of a7 run backwards)
         # ---- projector: feat = m3(gelu(m1(LN(ps_raw))))
-        ops.gemm_nn(L.EPI_NONE, self.dfeat, v['mlp1.m3w'], out=self.dg1)
-        self._wgrad(self.dfeat, self.g1, gv['mlp1.m3w'], bias_out=gv['mlp1.m3b'])
-        ops.gelu_bwd(self.z1, self.dg1, self.dz1)
-        self._wgrad(self.dz1, self.ps_ln, gv['mlp1.m1w'], bias_out=gv['mlp1.m1b'])
-        ops.gemm_nn(L.EPI_NONE, self.dz1, v['mlp1.m1w'], out=self.dln)
-        self._colsum(self.dln, self.ps_raw, gv['mlp1.m0w'], nt, C4, 3, 1e-5)
-        self._colsum(self.dln, None, gv['mlp1.m0b'], nt, C4, 0)
+        projector_backward(self.dfeat, v, gv, self.ps_raw, self.ps_ln, self.z1, self.g1, self.dg1, self.dz1, self.dln, self.col, self.rowstat)
         ops.layernorm_bwd(self.dln, self.ps_raw, v['mlp1.m0w'], None, self.dps, nt, C4, 1e-5)
         G_ = vis.image_size // vis.patch_size
         ops.pixel_unshuffle(self.dps, self.dvh, 1, G_, C, 1 if cfg.base.ps_version == 'v1' else 0)
@@ -340,11 +287,11 @@ class VLMGroup:
             ops.gemm(L.EPI_BIAS, self.vf[l], g('wfc2'), out=yrec, bias=g('bfc2'))                  # y2 again (the forward fuses it into the seam kernel)
             self._colsum(dvh, yrec, gg('ls2'), S, C, 1)
             ops.scale_cols(dvh, g('ls2'), dy, S, C)
-            self._wgrad(dy, self.vf[l], gg('wfc2'), bias_out=gg('bfc2'))
-            self._dgrad(dy, g('wfc2'), self.dvf)
+            wgrad_tn(dy, self.vf[l], gg('wfc2'), bias_out=gg('bfc2'))
+            dgrad_nn(dy, g('wfc2'), self.dvf, self.part)
             ops.gelu_bwd(self.vz[l], self.dvf, self.dvz)
-            self._wgrad(self.dvz, self.vx2[l], gg('wfc1'), bias_out=gg('bfc1'))
-            self._dgrad(self.dvz, g('wfc1'), dvx)
+            wgrad_tn(self.dvz, self.vx2[l], gg('wfc1'), bias_out=gg('bfc1'))
+            dgrad_nn(self.dvz, g('wfc1'), dvx, self.part)
             self._colsum(dvx, self.vhm[l], gg('n2w'), S, C, 3, eps)
             self._colsum(dvx, None, gg('n2b'), S, C, 0)
             ops.layernorm_bwd(dvx, self.vhm[l], g('n2w'), dvh, dvhm, S, C, eps)
@@ -352,8 +299,8 @@ class VLMGroup:
             ops.gemm(L.EPI_BIAS, self.vao[l], g('wproj'), out=yrec, bias=g('bproj'))
             self._colsum(dvhm, yrec, gg('ls1'), S, C, 1)
             ops.scale_cols(dvhm, g('ls1'), dy, S, C)
-            self._wgrad(dy, self.vao[l], gg('wproj'), bias_out=gg('bproj'))
-            self._dgrad(dy, g('wproj'), self.dvao)
+            wgrad_tn(dy, self.vao[l], gg('wproj'), bias_out=gg('bproj'))
+            dgrad_nn(dy, g('wproj'), self.dvao, self.part)
             q, k, vt = self.vq[l], self.vk[l], self.vvt[l]                                           # q carries the 1/sqrt(64) (VL_EPI_VIT_QKV)
             ops.gemm_raw(L.EPI_F32, q, k, sc, S, S, hdv, hdv, hdv, sp, batch=Hn, a_bs=sp * hdv, w_bs=sp * hdv, o_bs=S * sp)
             ops.gemm_raw_nn(L.EPI_F32, self.dvao, vt, dP, S, sp, hdv, C, sp, sp, batch=Hn, a_bs=hdv, w_bs=hdv * sp, o_bs=S * sp)
@@ -363,8 +310,8 @@ class VLMGroup:
             ops.scale_cols(dqkv, None, dqkv, S, C, alpha=hdv ** -0.5)                                                                              # -> d(raw q)
             ops.gemm_tn_grouped(dS, q, dqkv[:, C:], S, hdv, S, sp, hdv, 3 * C, 1, 0, 0, Hn, S * sp, sp * hdv, hdv)                                  # dk = dS^T q
             ops.gemm_tn_grouped(P, self.dvao, dqkv[:, 2 * C:], S, hdv, S, sp, C, 3 * C, 1, 0, 0, Hn, S * sp, hdv, hdv)                              # dv = P^T dO
-            self._wgrad(dqkv, self.vx1[l], gg('wqkv'), bias_out=gg('bqkv'))
-            self._dgrad(dqkv, g('wqkv'), dvx)
+            wgrad_tn(dqkv, self.vx1[l], gg('wqkv'), bias_out=gg('bqkv'))
+            dgrad_nn(dqkv, g('wqkv'), dvx, self.part)
             self._colsum(dvx, self.vh[l], gg('n1w'), S, C, 3, eps)
             self._colsum(dvx, None, gg('n1b'), S, C, 0)
             ops.layernorm_bwd(dvx, self.vh[l], g('n1w'), dvhm, dvh, S, C, eps)
@@ -379,26 +326,10 @@ class VLMGroup:
     def state_dict(self, grads=False):
         llm, vis = self.llm, self.vis
         v = self.fp.gview if grads else self.fp.view
-        nq, nkv, hd = llm.num_attention_heads, llm.num_key_value_heads, llm.head_dim
-        inv = torch.empty(hd, dtype=torch.long); inv[ops.head_perm(hd)] = torch.arange(hd)
         out = {'language_model.model.norm.weight': v['norm'].clone()}
         for i in range(llm.num_hidden_layers):
-            p = f'language_model.model.layers.{i}.'
-            w, b = v[f'l{i}.wqkv'], v[f'l{i}.bqkv']
-            idx = (torch.arange(nq + 2 * nkv)[:, None] * hd + inv[None, :]).reshape(-1).to(w.device)
-            wn, bn = w[idx], b[idx]
-            out[p + 'self_attn.q_proj.weight'], out[p + 'self_attn.q_proj.bias'] = wn[:nq * hd].clone(), bn[:nq * hd].clone()
-            out[p + 'self_attn.k_proj.weight'], out[p + 'self_attn.k_proj.bias'] = wn[nq * hd:(nq + nkv) * hd].clone(), bn[nq * hd:(nq + nkv) * hd].clone()
-            out[p + 'self_attn.v_proj.weight'], out[p + 'self_attn.v_proj.bias'] = wn[(nq + nkv) * hd:].clone(), bn[(nq + nkv) * hd:].clone()
-            out[p + 'self_attn.o_proj.weight'] = v[f'l{i}.wo'].clone()
-            gu = v[f'l{i}.wgu'].view(-1, 2, 16, llm.hidden_size)
-            out[p + 'mlp.gate_proj.weight'] = gu[:, 0].reshape(-1, llm.hidden_size).clone()
-            out[p + 'mlp.up_proj.weight'] = gu[:, 1].reshape(-1, llm.hidden_size).clone()
-            out[p + 'mlp.down_proj.weight'] = v[f'l{i}.wdown'].clone()
-            out[p + 'input_layernorm.weight'] = v[f'l{i}.ln_in'].clone()
-            out[p + 'post_attention_layernorm.weight'] = v[f'l{i}.ln_post'].clone()
-        for nm, k in [('m0w', 'mlp1.0.weight'), ('m0b', 'mlp1.0.bias'), ('m1w', 'mlp1.1.weight'), ('m1b', 'mlp1.1.bias'), ('m3w', 'mlp1.3.weight'), ('m3b', 'mlp1.3.bias')]:
-            out[k] = v['mlp1.' + nm].clone()
+            out.update(unpack_decoder_layer(v, f'l{i}.', f'language_model.model.layers.{i}.', llm))
+        out.update(unpack_mlp1(v))
         names = [('wqkv', 'attn.qkv.weight'), ('bqkv', 'attn.qkv.bias'), ('wproj', 'attn.proj.weight'), ('bproj', 'attn.proj.bias'), ('wfc1', 'mlp.fc1.weight'),
                  ('bfc1', 'mlp.fc1.bias'), ('wfc2', 'mlp.fc2.weight'), ('bfc2', 'mlp.fc2.bias'), ('n1w', 'norm1.weight'), ('n1b', 'norm1.bias'), ('n2w', 'norm2.weight'),
                  ('n2b', 'norm2.bias'), ('ls1', 'ls1'), ('ls2', 'ls2')]
