@@ -140,6 +140,14 @@ typedef struct {
 } VlaserAttnArgs;
 
 int vlaser_attn_prefill(const VlaserAttnArgs* args, vl_stream_t stream);
+/* (ABI 8, varlen) Block-diagonal causal attention over concatenated sequences: replaces flash_attn_varlen_func with cu_seqlens
+ * (qwen2_packed_training_patch.py:71-96) and the causal pass over a padded [B, S] batch (pad_data_collator.py:57-116, modeling_internvl_chat.py:143-243)
+ * without its pad rows.  args: batch 1, sq = kv_len = M = cu_seqlens[n_seqs] rows, head_dim 128; q / out rows, K rows and V^T columns are indexed by the
+ * GLOBAL row (M <= ld_vt); mode / causal_off / valid_len / n_splits are ignored; lse_out [n_q_heads, M] as above.  cu_seqlens: device int32 [n_seqs + 1],
+ * ascending from 0, arbitrary boundaries (lengths 0 and 1 allowed).  Query row r of sequence [lo, hi) sees key j iff lo <= j <= r: a workgroup walks the
+ * 64-key tiles between the lowest lo of its 64 rows and the diagonal.  Rows >= M of every output are not written.  n_seqs == 1 produces the bits of
+ * VL_ATTN_CAUSAL. */
+int vlaser_attn_varlen(const VlaserAttnArgs* args, const int32_t* cu_seqlens, int n_seqs, vl_stream_t stream);
 int vlaser_attn_skinny(const VlaserAttnArgs* args, vl_stream_t stream);
 
 /* ---- skinny (M <= 16 rows) weight-streaming GEMV on MFMA, HBM-bound --------------------------------------------
@@ -233,6 +241,15 @@ int vlaser_chain_down2(const void* x, int ldx, const void* W, float* out_f32, in
  * Key k is visible to query q iff k < kv_valid and (k <= q when causal != 0).  head_dim 128. */
 int vlaser_attn_bwd(const void* q, const void* k, const void* vt, const void* o, const void* d_o, const float* lse, float* delta_ws, void* dq, void* dk,
                     void* dv, int S, int n_q, int n_kv, int s_max, float scale, int causal, int kv_valid, int head_dim /* 128, checked */, vl_stream_t stream);
+/* (ABI 8, varlen) The backward of vlaser_attn_varlen (flash_attn_varlen_func's autograd, qwen2_packed_training_patch.py:71-96; the padded batch's causal
+ * backward, pad_data_collator.py:57-116): vlaser_attn_bwd's buffers with S = M = cu_seqlens[n_seqs] concatenated rows (M <= s_max, global row = cache slot)
+ * and the boundary table in place of `causal, kv_valid`.  Same two bodies in one launch: dQ per 64 query rows walks the key tiles from its rows' lowest
+ * sequence start to the diagonal; dK / dV per 64 keys walks the query tiles up to the end of the last sequence that owns one of those keys.  No atomics:
+ * run-to-run bit-identical; n_seqs == 1 (>= 2 rows) produces the bits of vlaser_attn_bwd(causal = 1).  A sequence of ONE token contributes exact zeros to dq / dk
+ * (softmax over a single key: dS = 0; formed in floating point it is ~1e-6 of rounding noise).  Rows >= M are not written. */
+int vlaser_attn_bwd_varlen(const void* q, const void* k, const void* vt, const void* o, const void* d_o, const float* lse, float* delta_ws, void* dq, void* dk,
+                           void* dv, int S, int n_q, int n_kv, int s_max, float scale, const int32_t* cu_seqlens, int n_seqs, int head_dim /* 128, checked */,
+                           vl_stream_t stream);
 
 /* Weight-gradient GEMM: out[M,N] (bf16) = At^T @ Wt, At [K,M] and Wt [K,N] row-major bf16 (contraction along rows).
  * dW = dY^T X of every nn.Linear on the SFT path (autograd of modeling_internvl_chat.py:194-203): At = dY [S,N_out],

@@ -62,6 +62,8 @@ _SIGS = {
     'vlaser_attn_prefill': [C.POINTER(AttnArgs), vp],
     'vlaser_attn_skinny': [C.POINTER(AttnArgs), vp],
     'vlaser_attn_bwd': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, vp],
+    'vlaser_attn_varlen': [C.POINTER(AttnArgs), vp, i32, vp],
+    'vlaser_attn_bwd_varlen': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, i32, i32, vp],
     'vlaser_skinny': [i32, i32, C.POINTER(SkinnyArgs), vp],
     'vlaser_chain_qkv_supported': [i32, i32, i32],
     'vlaser_chain_gu_supported': [i32, i32, i32, i32, i32],

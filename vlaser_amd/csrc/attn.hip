@@ -17,6 +17,7 @@
 //   FULL   : lim1 = kv_len                         (ViT, modeling_intern_vit.py:220-224: no mask)
 //   CAUSAL : lim1 = min(kv_len, i + 1 + causal_off)
 //   PREFIX : lim1 = valid_len[b]; rows >= blk_start additionally see [blk_start, kv_len)
+//   VARLEN : (vlaser_attn_varlen) n sequences back to back, row i of sequence [lo, hi) sees lo <= j <= i
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -122,7 +123,11 @@ struct DirectChunk {
 // per key and give each one twice the independent MFMA / exp work to overlap.
 // DENSE (ABI 8): VL_ATTN_DENSE -- every key tile is walked and the visibility comes from a.mask (fp32, additive): the mask values of a tile ride in registers with the tile's
 // K / V^T (requested one tile ahead, 4 consecutive keys = 16 bytes per score quad); its own instantiation, so the descriptor modes do not carry its registers
-template <int HD, int KS, int TK, bool TAIL = false, bool HOST = false, bool DENSE = false>      // HOST: TAIL with the tail rows hosted by the last full workgroup (p.tail_host; its own instantiation: +2 x 16 registers); TAIL: the FULL-mode tail handling (p.tail_key0 / p.tail_qb); its own instantiation, so the other shapes do not carry its registers
+// VARLEN (ABI 8, varlen): block-diagonal causal attention over concatenated sequences (vlaser_attn_varlen): CAUSAL with a per-row lower limit -- row r of sequence
+// [lo, hi) sees keys lo <= j <= r.  Query rows, K rows and V^T columns are all indexed by the GLOBAL row; the tiles stay on the global 64-key grid, so one sequence
+// starting at row 0 walks exactly the causal schedule (same bits).  Its own instantiation.  The boundary table rides in descriptor fields CAUSAL leaves unused
+// (a.valid_len = cu_seqlens [n + 1], a.n_splits = n: sequence i = rows [cu[i], cu[i + 1])), so the kernel argument block of every other instantiation is untouched.
+template <int HD, int KS, int TK, bool TAIL = false, bool HOST = false, bool DENSE = false, bool VARLEN = false>      // HOST: TAIL with the tail rows hosted by the last full workgroup (p.tail_host; its own instantiation: +2 x 16 registers); TAIL: the FULL-mode tail handling (p.tail_key0 / p.tail_qb); its own instantiation, so the other shapes do not carry its registers
 __global__ __launch_bounds__(256 * KS) void attn_prefill_kernel(AttnP p) {
   constexpr int DC = HD / 32;   // d-chunks of 32 for S^T
   constexpr int DT = HD / 16;   // d-tiles of 16 for O^T
@@ -187,6 +192,15 @@ __global__ __launch_bounds__(256 * KS) void attn_prefill_kernel(AttnP p) {
       blk_has2 = (q_last + a.q_row_off >= a.blk_start);
     }
   }
+  // VARLEN: first key of this lane's sequence, the largest such key among the wave's 16 rows (rows ascend with the lane: lane 15 holds it) and the first key
+  // TILE any of the workgroup's 64 rows sees (row qb * 64 belongs to the earliest sequence)
+  int seq_lo = 0, wave_lo = 0, t0 = 0;
+  if constexpr (VARLEN) {
+    const int32_t* cu = a.valid_len;
+    seq_lo = cu[vl_seq_of_row(cu, a.n_splits, min(q_row, a.sq - 1))];
+    wave_lo = __builtin_amdgcn_readlane(seq_lo, 15);
+    t0 = min(max(cu[vl_seq_of_row(cu, a.n_splits, qb * 64)], 0), qb * 64) / TK;      // (clamped: a corrupt table must not move a tile out of the cache)
+  }
 
   // Q fragments (MFMA-B: col = query fr, k = d)
   bf16x8 qf[DC];
@@ -223,7 +237,9 @@ __global__ __launch_bounds__(256 * KS) void attn_prefill_kernel(AttnP p) {
   if constexpr (TAIL) { if (p.tail_key0 >= 0) tailc.load(K, VT, p.tail_key0, a.kv_len, a.ld_vt, fr, g); }
 
   // key-tile schedule: [0, n1) then tiles overlapping [blk_start, kv_len)
-  const int n1 = (TAIL && p.tail_key0 >= 0) ? p.tail_key0 / TK : (blk_lim1 + TK - 1) / TK;
+  int n1_ = (TAIL && p.tail_key0 >= 0) ? p.tail_key0 / TK : (blk_lim1 + TK - 1) / TK;
+  if constexpr (VARLEN) n1_ -= t0;            // tiles [t0, diagonal]
+  const int n1 = n1_;
   int t2_lo = 0, t2_hi = 0;
   if (blk_has2) { t2_lo = max(n1, a.blk_start / TK); t2_hi = (a.kv_len + TK - 1) / TK; }
   const int n_tiles = n1 + max(0, t2_hi - t2_lo);
@@ -234,7 +250,10 @@ __global__ __launch_bounds__(256 * KS) void attn_prefill_kernel(AttnP p) {
   const float* mrow = nullptr;
   const float inv_scale = DENSE ? 1.0f / a.scale : 0.f;
   if constexpr (DENSE) mrow = a.mask + (size_t)b * a.mask_bs + (size_t)min(q_row, a.sq - 1) * a.mask_rs;
-  auto tile_key0 = [&](int it) { return (it < n1 ? it : t2_lo + (it - n1)) * TK; };
+  auto tile_key0 = [&](int it) {
+    if constexpr (VARLEN) return (t0 + it) * TK;
+    else return (it < n1 ? it : t2_lo + (it - n1)) * TK;
+  };
   auto load_tile = [&](int it) {
     const int key0 = tile_key0(it);
     if constexpr (DENSE) {
@@ -311,6 +330,11 @@ __global__ __launch_bounds__(256 * KS) void attn_prefill_kernel(AttnP p) {
             vis[c][t][r] = v;
             s[c][t][r] = v ? __builtin_fmaf(mv, inv_scale, s[c][t][r]) : s[c][t][r];
             if (v) mx = fmaxf(mx, s[c][t][r]);
+          } else if constexpr (MASKED && VARLEN) {
+            const int key = key0 + (cb + c) * 32 + g * 8 + t * 4 + r;
+            const bool v = key < lim1 && key >= seq_lo;
+            vis[c][t][r] = v;
+            if (v) mx = fmaxf(mx, s[c][t][r]);
           } else if constexpr (MASKED) {
             const int key = key0 + (cb + c) * 32 + g * 8 + t * 4 + r;
             const bool v = (key < lim1) || (key >= lo2 && key < hi2);
@@ -374,7 +398,9 @@ __global__ __launch_bounds__(256 * KS) void attn_prefill_kernel(AttnP p) {
     // skips the visibility arithmetic: the loop is VALU-issue bound (about 230 VALU + 17 transcendental instructions per tile
     // against 16 MFMAs at head_dim 64), and the masks were 40 % of it
     using all_c = std::integral_constant<int, NC>;
-    if (key0 + TK <= wave_lim1) tile_body(key0, std::false_type{}, all_c{}, 0, qf, m_run, l_run, o);
+    bool whole = key0 + TK <= wave_lim1;
+    if constexpr (VARLEN) whole = whole && key0 >= wave_lo;
+    if (whole) tile_body(key0, std::false_type{}, all_c{}, 0, qf, m_run, l_run, o);
     else tile_body(key0, std::true_type{}, all_c{}, 0, qf, m_run, l_run, o);
     if constexpr (HOST) {
       // the hosted rows: wave w takes the w-th 32-key chunk of EVERY tile (+25 % per wave and tile; a whole tile every fourth trip would double the time
@@ -743,6 +769,35 @@ extern "C" int vlaser_attn_prefill(const VlaserAttnArgs* a, vl_stream_t s) {
   if (a->head_dim == 128) VL_ATTN_PICK(128); else VL_ATTN_PICK(64);
 #undef VL_ATTN_PICK
 #undef VL_ATTN_LAUNCH
+  VL_LAUNCH_CHECK();
+  return 0;
+}
+
+// Block-diagonal causal attention over n_seqs concatenated sequences: the CAUSAL schedule of vlaser_attn_prefill (same tile / split choice, made from the same
+// numbers) with the per-row lower limit of the VARLEN instantiations.
+extern "C" int vlaser_attn_varlen(const VlaserAttnArgs* a, const int32_t* cu_seqlens, int n_seqs, vl_stream_t s) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(s);
+  VL_CHECK(a && a->q && a->k && a->vt && a->out && cu_seqlens, "vlaser_attn_varlen: null pointer");
+  VL_CHECK(a->head_dim == 128, "vlaser_attn_varlen: head_dim %d -- the varlen kernels are built for head_dim 128 (Qwen2.5)", a->head_dim);
+  VL_CHECK(a->n_q_heads % a->n_kv_heads == 0, "vlaser_attn_varlen: GQA group mismatch");
+  VL_CHECK(a->ld_vt % 64 == 0, "vlaser_attn_varlen: V^T row length must be padded to a multiple of 64 keys");
+  VL_CHECK(n_seqs >= 1 && a->sq >= 1, "vlaser_attn_varlen: empty");
+  VL_CHECK(a->batch == 1 && a->kv_len == a->sq, "vlaser_attn_varlen: one batch element of sq = kv_len = cu_seqlens[n_seqs] concatenated rows");
+  VL_CHECK(a->sq <= a->ld_vt, "vlaser_attn_varlen: %d rows exceed the cache (%d): the key of global row r lives in cache slot r", a->sq, a->ld_vt);
+  AttnP p; p.a = *a; p.tail_key0 = -1; p.tail_qb = -1; p.tail_host = 0;
+  p.a.mode = VL_ATTN_CAUSAL; p.a.causal_off = 0;
+  p.a.valid_len = cu_seqlens; p.a.n_splits = n_seqs;      // the VARLEN instantiations read the boundary table from these two (unused by CAUSAL)
+  const dim3 grid((a->sq + 63) / 64, a->n_q_heads, 1);
+  const int ks = ((long)grid.x * grid.y <= 96 && a->kv_len > 64) ? 2 : 1;      // vlaser_attn_prefill's rule for head_dim 128 / CAUSAL
+  if (ks == 2) {
+    constexpr int lds = 2 * (2 * 64 * 128 * 2);      // two groups' K + V^T tiles (>= the merge area, 34 816 bytes)
+    if (int rc = set_max_lds_once(attn_prefill_kernel<128, 2, 64, false, false, false, true>, lds)) return rc;
+    hipLaunchKernelGGL((attn_prefill_kernel<128, 2, 64, false, false, false, true>), grid, dim3(512), lds, stream, p);
+  } else {
+    constexpr int lds = 2 * 64 * 128 * 2;
+    if (int rc = set_max_lds_once(attn_prefill_kernel<128, 1, 64, false, false, false, true>, lds)) return rc;
+    hipLaunchKernelGGL((attn_prefill_kernel<128, 1, 64, false, false, false, true>), grid, dim3(256), lds, stream, p);
+  }
   VL_LAUNCH_CHECK();
   return 0;
 }

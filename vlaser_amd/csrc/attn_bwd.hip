@@ -16,6 +16,10 @@
 //   * the other operand of those products is the P / dS tile just computed: its 16-row MFMA tiles are assigned to rows c*32 + 16t + (0..15), so lane
 //     group g holds rows 16t + 4g + r -- e = 4t + r is then exactly the transposing read's k order, and the accumulator registers convert to an operand
 //     fragment with a pack, no LDS round trip.
+//
+// VARLEN (vlaser_attn_bwd_varlen): the same two bodies over n concatenated sequences (block-diagonal causal; the SFT step's batch-rows mode).  Each lane bisects
+// cu_seqlens once in the prologue: the dQ half for the first key of its query's sequence, the dK / dV half for the end of its key's sequence; the tile walks are
+// bounded by the workgroup's lowest sequence start / the end of the last sequence that owns one of its keys.  Own instantiations: the causal ones are untouched.
 #include "common.h"
 #include "../../include/vlaser_hip.h"
 
@@ -55,6 +59,10 @@ struct AttnBwdP {
   int S, n_q, n_kv, s_max;
   float scale;
   int causal, kv_valid;
+  // (ABI 8, varlen) VARLEN instantiations only: the S rows are n_seqs sequences laid back to back, sequence i = rows [cu_seqlens[i], cu_seqlens[i + 1]);
+  // query q of sequence [lo, hi) sees key k iff lo <= k <= q.  q / k / v^T rows are all indexed by the global row; the tiles stay on the global 64-row grid.
+  const int32_t* cu_seqlens;
+  int n_seqs;
 };
 
 // 8 values of one row in the transposing read's k order: columns c0 + 16h + 4g + j  (two 8-byte loads)
@@ -68,7 +76,7 @@ __device__ __forceinline__ bf16x8 ab_load_tr_order(const bf16_t* row, int c0, in
 // TK = keys per staged tile; KS = wave groups (of 4 waves) that take the key tiles in turn and merge their dQ sums at the end: at SFT lengths the grid
 // is 108 workgroups on 256 CUs and one wave per SIMD runs LDS reads, MFMAs and the softmax arithmetic back to back -- a second group per
 // workgroup gives every SIMD a second instruction stream to overlap them with and halves the chain of tile iterations.
-template <int TK, int KS, bool WRITE_D>
+template <int TK, int KS, bool WRITE_D, bool VARLEN = false>
 __device__ __forceinline__ void attn_bwd_dq_body(const AttnBwdP& p) {
   constexpr int HD = 128, DC = 4, DT = 8, NCH = TK / 32, NLD = TK / 16, PV = TK == 64 ? AB_PV : AB_PQ;
   constexpr int TILE_B = TK * AB_PQ + 128 * PV, MERGE_WAVE = DT * 4 * 64 * 4;
@@ -104,6 +112,18 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnBwdP& p) {
   const float lse = p.lse[(size_t)h * p.S + qc];
   if (WRITE_D && g == 0 && grp == 0 && qi < p.S) p.delta[(size_t)h * p.S + qi] = D;      // (the one-launch form gets D from attn_bwd_delta_kernel: same bits)
   const int klim = qi < p.S ? (p.causal ? min(qi + 1, p.kv_valid) : p.kv_valid) : 0;
+  // VARLEN: first key of this row's sequence; t0 = the first key tile any row of the workgroup sees (row qb * 64 belongs to the earliest sequence)
+  // solo: a sequence of ONE token -- softmax over a single key is P = 1 whatever the score, so dS = P (dP - D) is exactly 0.  Formed in floating point it is the
+  // difference of two equal 128-term sums taken in different orders (dP in an MFMA, D in FMAs): ~1e-6 of noise in a gradient that is identically zero.  The
+  // first row of a LONGER sequence sees one key too; it keeps the causal kernels' arithmetic (one sequence of >= 2 rows = their bits).
+  int seq_lo = 0, t0 = 0;
+  bool solo = false;
+  if constexpr (VARLEN) {
+    const int si = vl_seq_of_row(p.cu_seqlens, p.n_seqs, qc);
+    seq_lo = p.cu_seqlens[si];
+    solo = p.cu_seqlens[si + 1] - seq_lo == 1;
+    t0 = min(max(p.cu_seqlens[vl_seq_of_row(p.cu_seqlens, p.n_seqs, qb * 64)], 0), qb * 64) / TK;      // (clamped: a corrupt table must not move a tile out of the cache)
+  }
   const float sc = p.scale * 1.4426950408889634f;
   f32x4 dqT[DT];
 #pragma unroll
@@ -132,14 +152,14 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnBwdP& p) {
       *reinterpret_cast<u32x4*>(vs + (c / (TK / 8)) * PV + (c % (TK / 8)) * 16) = rv[i];
     }
   };
-  const int n_it = (n_tiles + KS - 1) / KS;                   // workgroup-uniform trip count: a group past its last tile idles at the barriers
+  const int n_it = (n_tiles - t0 + KS - 1) / KS;              // workgroup-uniform trip count: a group past its last tile idles at the barriers
   if (n_tiles > 0) {
-    load_tile(min(grp, n_tiles - 1));
+    load_tile(min(t0 + grp, n_tiles - 1));
     store_tile(0);
-    load_tile(min(grp + KS, n_tiles - 1));
+    load_tile(min(t0 + grp + KS, n_tiles - 1));
   }
   for (int itg = 0; itg < n_it; ++itg) {
-    const int it = itg * KS + grp;
+    const int it = t0 + itg * KS + grp;
     __syncthreads();                   // tile itg is in its buffer for every wave, and every wave is done reading the other buffer (tile itg-1)
     Ks = tiles + (itg & 1) * TILE_B;
     Vs = Ks + TK * AB_PQ;
@@ -166,8 +186,8 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnBwdP& p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = key0 + c * 32 + t * 16 + g * 4 + r;
-          const float pe = key < klim ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], sc, -lse)) : 0.f;
-          dsv[t * 4 + r] = pe * (dp[r] - D) * p.scale;
+          const float pe = (key < klim && (!VARLEN || key >= seq_lo)) ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], sc, -lse)) : 0.f;
+          dsv[t * 4 + r] = (VARLEN && solo) ? 0.f : pe * (dp[r] - D) * p.scale;
         }
       }
       dsf[c] = as_bf16x8(u32x4{pack_bf16x2(dsv[0], dsv[1]), pack_bf16x2(dsv[2], dsv[3]), pack_bf16x2(dsv[4], dsv[5]), pack_bf16x2(dsv[6], dsv[7])});
@@ -215,7 +235,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnBwdP& p) {
 }
 
 // ---------------------------------------------------------------------------------------------- dK, dV (one partial per Q head)
-template <int TK, int KS>      // TK queries per staged tile, KS wave groups taking the query tiles in turn (as above)
+template <int TK, int KS, bool VARLEN = false>      // TK queries per staged tile, KS wave groups taking the query tiles in turn (as above)
 __device__ __forceinline__ void attn_bwd_dkv_body(const AttnBwdP& p) {
   constexpr int HD = 128, DC = 4, DT = 8, NCH = TK / 32, NLD = TK / 16;
   constexpr int TILE_B = 2 * TK * AB_PQ + 2 * TK * 4, MERGE_WAVE = 2 * DT * 4 * 64 * 4;
@@ -245,7 +265,17 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnBwdP& p) {
   f32x4 dvT[DT], dkT[DT];
 #pragma unroll
   for (int i = 0; i < DT; ++i) { dvT[i] = f32x4{0, 0, 0, 0}; dkT[i] = f32x4{0, 0, 0, 0}; }
-  const int n_qt = (p.S + TK - 1) / TK;
+  // VARLEN: this key is seen by the queries of its own sequence only (key <= q < seq_hi); the workgroup walks the query tiles up to the end of the LAST
+  // sequence that owns one of its 64 keys
+  int seq_hi = p.S, blk_hi = p.S;
+  bool solo = false;                  // this key is a one-token sequence: dS = 0 exactly (see the dQ body); P still carries dO into dV
+  if constexpr (VARLEN) {
+    const int si = vl_seq_of_row(p.cu_seqlens, p.n_seqs, min(key, p.S - 1));
+    seq_hi = p.cu_seqlens[si + 1];
+    solo = seq_hi - p.cu_seqlens[si] == 1;
+    blk_hi = min(p.cu_seqlens[vl_seq_of_row(p.cu_seqlens, p.n_seqs, min(kb * 64 + 63, p.S - 1)) + 1], p.S);
+  }
+  const int n_qt = (blk_hi + TK - 1) / TK;
   const int it0 = p.causal ? (kb * 64) / TK : 0;              // causal: query tiles left of this key tile see none of its keys
   u32x4 rq[NLD], ro[NLD];
   float rl = 0.f, rd = 0.f;
@@ -311,10 +341,10 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnBwdP& p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int ql = c * 32 + t * 16 + g * 4 + r, qq = q0 + ql;
-          const bool vis = key_ok && qq < p.S && (!p.causal || key <= qq);
+          const bool vis = key_ok && qq < (VARLEN ? seq_hi : p.S) && (!p.causal || key <= qq);
           const float pe = vis ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], sc, -lse_s[ql])) : 0.f;
           pv[t * 4 + r] = pe;
-          dsv[t * 4 + r] = pe * (dp[r] - del_s[ql]) * p.scale;
+          dsv[t * 4 + r] = (VARLEN && solo) ? 0.f : pe * (dp[r] - del_s[ql]) * p.scale;
         }
       }
       pf[c] = as_bf16x8(u32x4{pack_bf16x2(pv[0], pv[1]), pack_bf16x2(pv[2], pv[3]), pack_bf16x2(pv[4], pv[5]), pack_bf16x2(pv[6], pv[7])});
@@ -392,6 +422,12 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_both_kernel(AttnBwdP p) {
   else attn_bwd_dkv_body<TK, KS>(p);
 }
 
+template <int TK, int KS>
+__global__ __launch_bounds__(256 * KS) void attn_bwd_both_varlen_kernel(AttnBwdP p) {
+  if (blockIdx.z == 0) attn_bwd_dq_body<TK, KS, false, true>(p);
+  else attn_bwd_dkv_body<TK, KS, true>(p);
+}
+
 extern "C" int vlaser_attn_bwd(const void* q, const void* k, const void* vt, const void* o, const void* d_o, const float* lse, float* delta_ws, void* dq, void* dk,
                                void* dv, int S, int n_q, int n_kv, int s_max, float scale, int causal, int kv_valid, int head_dim, vl_stream_t s) {
   VL_CHECK(q && k && vt && o && d_o && lse && delta_ws && dq && dk && dv, "vlaser_attn_bwd: null pointer");
@@ -422,6 +458,35 @@ extern "C" int vlaser_attn_bwd(const void* q, const void* k, const void* vt, con
   }
   if (ks == 2) AB_LAUNCH(2) else AB_LAUNCH(1)
 #undef AB_LAUNCH
+  VL_LAUNCH_CHECK();
+  return 0;
+}
+
+// Backward of vlaser_attn_varlen: the one-launch form above (D first, then both halves side by side) with the VARLEN bodies; the wave-group rule is
+// vlaser_attn_bwd's, made from the same number, so one sequence (of >= 2 rows: see `solo`) starting at row 0 produces the causal call's bits.
+extern "C" int vlaser_attn_bwd_varlen(const void* q, const void* k, const void* vt, const void* o, const void* d_o, const float* lse, float* delta_ws, void* dq,
+                                      void* dk, void* dv, int S, int n_q, int n_kv, int s_max, float scale, const int32_t* cu_seqlens, int n_seqs, int head_dim,
+                                      vl_stream_t s) {
+  VL_CHECK(q && k && vt && o && d_o && lse && delta_ws && dq && dk && dv && cu_seqlens, "vlaser_attn_bwd_varlen: null pointer");
+  VL_CHECK(head_dim == 128, "vlaser_attn_bwd_varlen: head_dim %d -- the kernels are built for head_dim 128 (Qwen2.5)", head_dim);
+  VL_CHECK(S >= 1 && n_seqs >= 1 && n_kv >= 1 && n_q % n_kv == 0 && s_max % 64 == 0, "vlaser_attn_bwd_varlen: bad geometry");
+  VL_CHECK(S <= s_max, "vlaser_attn_bwd_varlen: %d rows exceed the cache (%d): the key of global row r lives in cache slot r", S, s_max);
+  AttnBwdP p;
+  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.vt = (const bf16_t*)vt; p.o = (const bf16_t*)o; p.d_o = (const bf16_t*)d_o;
+  p.lse = lse; p.delta = delta_ws; p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
+  p.S = S; p.n_q = n_q; p.n_kv = n_kv; p.s_max = s_max; p.scale = scale; p.causal = 1; p.kv_valid = S;
+  p.cu_seqlens = cu_seqlens; p.n_seqs = n_seqs;
+  const dim3 grid((S + 63) / 64, n_q);
+#define AB_LAUNCH_VARLEN(KS_)                                                                                                              \
+  {                                                                                                                                        \
+    const int lds_q = 2 * KS_ * (64 * AB_PQ + 128 * AB_PV), lds_kv = 2 * KS_ * (2 * 64 * AB_PQ + 2 * 64 * 4);                              \
+    const int lds_b = lds_q > lds_kv ? lds_q : lds_kv;                                                                                     \
+    if (int rc = set_max_lds_once(attn_bwd_both_varlen_kernel<64, KS_>, lds_b)) return rc;                                                 \
+    hipLaunchKernelGGL(attn_bwd_delta_kernel, grid, dim3(256), 0, (hipStream_t)s, p);                                                      \
+    hipLaunchKernelGGL((attn_bwd_both_varlen_kernel<64, KS_>), dim3(grid.x, grid.y, 2), dim3(256 * KS_), lds_b, (hipStream_t)s, p);        \
+  }
+  if (S > 128) AB_LAUNCH_VARLEN(2) else AB_LAUNCH_VARLEN(1)
+#undef AB_LAUNCH_VARLEN
   VL_LAUNCH_CHECK();
   return 0;
 }

@@ -133,6 +133,17 @@ __device__ __forceinline__ void st_global_16(void* p, u32x4 v) { *reinterpret_ca
 typedef const __attribute__((address_space(4))) int32_t* vl_cptr_i32;
 __device__ __forceinline__ int vl_sload_i32(const int32_t* p) { return *reinterpret_cast<vl_cptr_i32>(reinterpret_cast<uintptr_t>(p)); }
 
+// Varlen attention (ABI 8, varlen): the sequence that owns global row `row` of n concatenated sequences, cu[0] = 0 <= row < cu[n] (cu ascending; an empty
+// sequence owns no row): the largest i with cu[i] <= row, by bisection -- ceil(log2 n) dependent reads of a table that sits in L2 after the first workgroup.
+__device__ __forceinline__ int vl_seq_of_row(const int32_t* cu, int n, int row) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (cu[mid] <= row) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // ---- kernel arguments in ONE scalar-memory round trip.  hipcc issues the s_load of a by-value argument struct piecemeal, where each field is first
 // needed, with an `s_waitcnt lgkmcnt(0)` in front of every first use: the <= 16-row kernels started with 3-6 SERIALISED round trips to the kernarg segment
 // (scalar cache cold at every kernel start) before their first global load went out (r04, read in the ISA: skinny_kernel 4 rounds, the since-removed attention + o_proj kernel 6).

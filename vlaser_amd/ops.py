@@ -218,6 +218,35 @@ def attn_bwd(q, k, vt, o, d_o, lse, delta_ws, dq, dk, dv, S, n_q, n_kv, s_max, s
                                     dk.data_ptr(), dv.data_ptr(), S, n_q, n_kv, s_max, scale, int(causal), S if kv_valid is None else kv_valid, head_dim, _stream()), 'vlaser_attn_bwd')
 
 
+def _check_cu_seqlens(cu_seqlens, M, cu_host, what):
+    """Host-side validation of a varlen call, before any launch: the device table's type / length, and -- when the caller hands its host copy over
+    (the trainer always holds one) -- that it ascends from 0 to M."""
+    if not (cu_seqlens.is_cuda and cu_seqlens.dtype == torch.int32 and cu_seqlens.dim() == 1 and cu_seqlens.is_contiguous() and cu_seqlens.numel() >= 2):
+        raise L.VlaserHipError(f'{what}: cu_seqlens must be a contiguous device int32 [n_seqs + 1] tensor')
+    n = cu_seqlens.numel() - 1
+    if cu_host is not None:
+        cu = [int(x) for x in cu_host]
+        if len(cu) != n + 1 or cu[0] != 0 or cu[-1] != M or any(b < a for a, b in zip(cu, cu[1:])):
+            raise L.VlaserHipError(f'{what}: cu_seqlens must ascend from 0 to the number of rows ({M}), got {cu}')
+    return n
+
+
+def attn_varlen(q, k, vt, out, M, n_q, n_kv, hd, s_max, scale, cu_seqlens, lse_out=None, cu_host=None):
+    """Block-diagonal causal attention over concatenated sequences (csrc/attn.hip, VARLEN): q / out [M, n_q*hd], k [n_kv, s_max, hd], vt [n_kv, hd, s_max]
+    indexed by the global row, cu_seqlens device int32 [n + 1]; `cu_host`: the same numbers on the host, validated before the launch."""
+    n = _check_cu_seqlens(cu_seqlens, M, cu_host, 'vlaser_attn_varlen')
+    a = _attn_args(q, k, vt, out, 1, M, M, n_q, n_kv, hd, (M * n_q * hd, hd, n_q * hd), (n_kv * s_max * hd, s_max * hd), (n_kv * hd * s_max, hd * s_max),
+                   (M * n_q * hd, n_q * hd), s_max, scale, L.ATTN_CAUSAL, lse_out=lse_out)
+    L.check(L.lib().vlaser_attn_varlen(C.byref(a), cu_seqlens.data_ptr(), n, _stream()), 'vlaser_attn_varlen')
+
+
+def attn_bwd_varlen(q, k, vt, o, d_o, lse, delta_ws, dq, dk, dv, M, n_q, n_kv, s_max, scale, cu_seqlens, head_dim=128, cu_host=None):
+    """Fused backward of `attn_varlen` (csrc/attn_bwd.hip, VARLEN): `attn_bwd`'s buffers over the M concatenated rows, one dk / dv partial per Q head."""
+    n = _check_cu_seqlens(cu_seqlens, M, cu_host, 'vlaser_attn_bwd_varlen')
+    L.check(L.lib().vlaser_attn_bwd_varlen(q.data_ptr(), k.data_ptr(), vt.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), delta_ws.data_ptr(), dq.data_ptr(),
+                                           dk.data_ptr(), dv.data_ptr(), M, n_q, n_kv, s_max, scale, cu_seqlens.data_ptr(), n, head_dim, _stream()), 'vlaser_attn_bwd_varlen')
+
+
 def attn_splits(kv_len):
     """Key splits of the skinny attention: about 2 chunks (of 32 keys) per block, at most 8 splits (measured: 389 keys,
     1/2/4/7 splits -> 13.5/9.5/7.7/6.3 us per launch)."""

@@ -20,6 +20,7 @@ import math
 import contextlib
 import os
 from types import SimpleNamespace
+from typing import NamedTuple
 
 import torch
 
@@ -86,18 +87,57 @@ def plan_flat_layout(cfg, world, bucket_layers=4, device='cpu'):
     return fp, cut_buckets(bounds)
 
 
+class BatchRowsPlan(NamedTuple):
+    """Row layout of one per-device batch run as ONE varlen pass (`plan_batch_rows`); host tensors only."""
+    ids: torch.Tensor             # int64 [M]: the samples' ids back to back, each trimmed to its own length (no pad rows)
+    pos_ids: torch.Tensor         # int32 [M]: position inside the sample (restarts at 0)
+    cu_seqlens: torch.Tensor      # int32 [B + 1]: sample b = rows [cu[b], cu[b + 1])
+    targets: torch.Tensor         # int64 [M]: label of the NEXT token of the same sample, -100 where nothing is predicted (always on a sample's last row)
+    rows: torch.Tensor            # int64 [R]: the supervised rows, ascending
+    R: int                        # supervised positions of the whole batch: the loss is their mean
+    n_img: int                    # <IMG_CONTEXT> rows: the visual tokens the batch's real tiles must deliver, in order
+
+
+def plan_batch_rows(samples, img_context_token_id):
+    """`SFTModel._split_batch`'s samples `(pixel_values, ids [1, L_b], labels [1, L_b], image_flags, R_b)` laid out back to back for one forward / backward over
+    M = sum L_b rows: what the reference's padded [B, S] pass computes (pad_data_collator.py:57-116, modeling_internvl_chat.py:143-243) without its pad rows.
+    Positions restart at 0 in every sample; the shift of the labels happens INSIDE each sample, so its last token predicts nothing (never the first token of
+    the next sample).  Pure host function: no GPU, no model."""
+    ids, pos, tgt, cu, n_img = [], [], [], [0], 0
+    for smp in samples:
+        idb, lbb = smp[1].reshape(-1).to(torch.int64), smp[2].reshape(-1).to(torch.int64)
+        Lb = int(idb.numel())
+        if Lb < 1 or lbb.numel() != Lb:
+            raise ValueError(f'a sample needs >= 1 token and as many labels as ids (got {Lb} ids, {lbb.numel()} labels)')
+        t = torch.full((Lb,), -100, dtype=torch.int64)
+        t[:Lb - 1] = lbb[1:]
+        ids.append(idb); tgt.append(t)
+        pos.append(torch.arange(Lb, dtype=torch.int32))
+        cu.append(cu[-1] + Lb)
+        n_img += int((idb == img_context_token_id).sum())
+    ids, tgt = torch.cat(ids), torch.cat(tgt)
+    rows = (tgt != -100).nonzero().flatten()
+    if sum(int(smp[4]) for smp in samples) != int(rows.numel()):
+        raise ValueError('the samples\' supervised-position counts do not add up to the plan\'s')
+    return BatchRowsPlan(ids, torch.cat(pos), torch.tensor(cu, dtype=torch.int32), tgt, rows, int(rows.numel()), n_img)
+
+
 class SFTModel(ParamGroup):
     """Trainable Vlaser-2B SFT step (per rank).  `step(pixel_values, input_ids, labels)` runs forward, backward, the
     gradient exchange and the optimizer update and returns the (rank-local) loss."""
 
     def __init__(self, cfg: VlaserConfig, device='cuda', max_seq_len=576, max_tiles=1, lr=2e-5, weight_decay=0.05, betas=(0.9, 0.999),
-                 eps=1e-8, max_grad_norm=1.0, process_group=None, bucket_layers=4, seed_state_dict=None, recompute=False, attn_bwd_block=1024, attn_bwd='fused'):
+                 eps=1e-8, max_grad_norm=1.0, process_group=None, bucket_layers=4, seed_state_dict=None, recompute=False, attn_bwd_block=1024, attn_bwd='fused',
+                 batch_rows=False, max_batch_tokens=None):
         L.lib()
         if not torch.cuda.is_available():
             raise L.VlaserHipError('vlaser_amd needs an MI355X (gfx950) GPU: there is no CPU fallback')
         self.cfg, self.device = cfg, torch.device(device)
         self.llm = cfg.llm
-        self.S_max = (max_seq_len + 63) // 64 * 64
+        self.S_max = (max_seq_len + 63) // 64 * 64          # bounds ONE sample
+        # rows the activation / gradient / cache / lse / split-K buffers hold: one sample, or -- `batch_rows` -- the M concatenated rows of a per-device
+        # batch (`max_batch_tokens`; grown on first need otherwise, `_grow_rows`)
+        self.M_max = max(self.S_max, ((max_batch_tokens or 0) + 63) // 64 * 64)
         self.lr, self.wd, self.betas, self.eps, self.max_grad_norm = lr, weight_decay, betas, eps, max_grad_norm
         self.pg = process_group
         self.world = 1 if process_group is None else torch.distributed.get_world_size(process_group)
@@ -117,6 +157,13 @@ class SFTModel(ParamGroup):
         self.attn_bwd_mode = os.environ.get('VLASER_SFT_ATTN_BWD', attn_bwd)
         if self.attn_bwd_mode not in ('fused', 'materialised'):
             raise ValueError(f'VLASER_SFT_ATTN_BWD={self.attn_bwd_mode!r}: fused | materialised')
+        # batch_rows (VLASER_SFT_BATCH_ROWS=1): a micro-batch of B > 1 samples runs as ONE forward / backward over its concatenated rows (varlen attention,
+        # csrc/attn.hip + attn_bwd.hip `VARLEN`) instead of B passes of one sample each.  Off by default: the one-sample path is unchanged bit for bit.
+        env_br = os.environ.get('VLASER_SFT_BATCH_ROWS')
+        self.batch_rows = bool(batch_rows) if env_br is None else env_br == '1'
+        if self.batch_rows and self.attn_bwd_mode == 'materialised':
+            raise ValueError('batch_rows needs the fused attention backward (the materialised score matrices know one sequence): attn_bwd=\'fused\'')
+        self._varlen = None                       # (device cu_seqlens, host list) while a batch-rows pass is being queued
         self.ag_events = {}                       # bucket -> event of its last parameter all-gather (data parallel only)
         self.opt_stream = self.comm_stream = None  # made by load_state_dict (`_alloc_workspace`)
         # per-step state of the gradient norm taken from the producers (`_run_weighted_main`) and of the buffers that are cleared lazily
@@ -161,11 +208,16 @@ class SFTModel(ParamGroup):
         return self
 
     def _alloc_workspace(self):
+        self._alloc_buffers()
+        self._alloc_streams()
+
+    def _alloc_buffers(self):
+        """Every per-row buffer of the step, for `M_max` rows (also what `_grow_rows` re-runs: buffers only, no stream, no exchange)."""
         cfg, llm, dev = self.cfg, self.llm, self.device
         H, I, V = llm.hidden_size, llm.intermediate_size, llm.vocab_size
         nq, nkv, hd = llm.num_attention_heads, llm.num_key_value_heads, llm.head_dim
         NQ = (nq + 2 * nkv) * hd
-        S, Lyr = self.S_max, llm.num_hidden_layers
+        S, Lyr = self.M_max, llm.num_hidden_layers
         z = lambda *s, dt=BF: torch.zeros(*s, dtype=dt, device=dev)
         C4 = cfg.vision.hidden_size * 4
         # the dgrad GEMMs read the forward weights as stored (vlaser_gemm_nn): no transposed copies (r01/r02 kept 3.5 GB of W^T and
@@ -208,6 +260,21 @@ class SFTModel(ParamGroup):
         self.rank_ws = torch.zeros(S, dtype=torch.int32, device=dev)
         self.pos_all = torch.arange(S, dtype=torch.int32, device=dev)
         self._alloc_projector_ws()
+        self._wgrad_pad_S = None
+        self.norm_parts = None                  # (the embedding's slots follow the row count: re-planned on next use)
+
+    def _grow_rows(self, M):
+        """A batch-rows micro-batch with more rows than the buffers hold: re-allocate them (buffers only), behind everything that may still use the old ones."""
+        if M > self.M_max:
+            self.wait_optimizer()
+            self._join_wgrad()
+            self.M_max = (M + 63) // 64 * 64
+            self._alloc_buffers()
+            if self._fused_norm:                # (a step already under way planned its slots for the old row count)
+                self._plan_fused_norm()
+
+    def _alloc_streams(self):
+        dev = self.device
         # The exchange (data parallel only).  VLASER_DP_EXCHANGE=pg (default): torch's ProcessGroupNCCL from a comm stream.  =capi: RCCL's C API on a communicator and a
         # stream of this package's own (rccl_capi.py), that stream CU-masked to the last VLASER_DP_COMM_CUS CUs (default 32; 0 = no masks) and EVERY compute stream of the
         # step (main, weight gradients, optimizer) masked to the rest -- RCCL's channel workgroups then never share a CU with a GEMM workgroup (x1.13 instead of
@@ -273,7 +340,7 @@ class SFTModel(ParamGroup):
         self.dvit, self.dg1, self.dz1, self.dln = z(nt, H), z(nt, H), z(nt, H), z(nt, C4)
         I = self.llm.intermediate_size
         NQ = (self.llm.num_attention_heads + 2 * self.llm.num_key_value_heads) * self.llm.head_dim
-        self.rowstat = torch.zeros(2 * max(self.S_max, nt) + 16 * max(2 * I, NQ, C4, H), dtype=F32, device=dev)   # colsum scratch
+        self.rowstat = torch.zeros(2 * max(self.M_max, nt) + 16 * max(2 * I, NQ, C4, H), dtype=F32, device=dev)   # colsum scratch
 
     def _grow_tiles(self, T):
         """A sample with more tiles than the workspaces were built for (dynamic-resolution SFT: up to 12 + thumbnail, plus dummy
@@ -337,8 +404,8 @@ class SFTModel(ParamGroup):
                     self.norm_slot[name] = (n, cap)
                     n += cap
                 elif name == 'embed':
-                    self.norm_slot[name] = (n, self.S_max)
-                    n += self.S_max
+                    self.norm_slot[name] = (n, self.M_max)
+                    n += self.M_max
                 else:
                     chunks += [(off + c0, min(8192, numel - c0)) for c0 in range(0, numel, 8192)]
             tab = torch.tensor(chunks, dtype=torch.int64, device=dev).reshape(-1, 2) if chunks else None
@@ -422,8 +489,12 @@ class SFTModel(ParamGroup):
                  rope_cos=self.rope[0], rope_sin=self.rope[1], pos_ids=pos, n_q_heads=nq, n_kv_heads=nkv, s_max=self.cache.s_max,
                  tok_per_batch=S, slot_base=0)
         ks, vs = self.cache.strides()
-        ops.attn_prefill(q, self.cache.k[j], self.cache.vt[j], ao, 1, S, S, nq, nkv, hd, (S * nq * hd, hd, nq * hd), ks, vs,
-                         (S * nq * hd, nq * hd), self.cache.s_max, hd ** -0.5, L.ATTN_CAUSAL, lse_out=self.lse[j])
+        if self._varlen is not None:      # batch rows: S = the M concatenated rows, K / V in cache slot = global row, causal inside each sample
+            ops.attn_varlen(q, self.cache.k[j], self.cache.vt[j], ao, S, nq, nkv, hd, self.cache.s_max, hd ** -0.5, self._varlen[0], lse_out=self.lse[j],
+                            cu_host=self._varlen[1])
+        else:
+            ops.attn_prefill(q, self.cache.k[j], self.cache.vt[j], ao, 1, S, S, nq, nkv, hd, (S * nq * hd, hd, nq * hd), ks, vs,
+                             (S * nq * hd, nq * hd), self.cache.s_max, hd ** -0.5, L.ATTN_CAUSAL, lse_out=self.lse[j])
         sp = ops.gemm_splits(S, H, nq * hd)
         ops.gemm(L.EPI_PARTIAL, ao, v[f'l{i}.wo'], out_f32=self.part, k_splits=sp)
         ops.reduce_norm(h_in, self.part, sp, S, H, h2, x2, norm=1, norm_w=v[f'l{i}.ln_post'], eps=llm.rms_norm_eps)
@@ -444,8 +515,9 @@ class SFTModel(ParamGroup):
             ops.reduce_norm(h2, self.part, sp, S, llm.hidden_size, h_out, x_out, norm=1, norm_w=norm_w, eps=llm.rms_norm_eps)
 
     # ------------------------------------------------------------------ forward (loss) + backward (grads into self.fp.g)
-    def forward_backward(self, pixel_values, input_ids, labels, image_flags=None, on_bucket_ready=None):
-        """Loss + gradients of ONE sample.  The ~850 launches of the call all go to the stream that is current at entry: its handle is looked up once and
+    def forward_backward(self, pixel_values, input_ids, labels, image_flags=None, on_bucket_ready=None, plan=None):
+        """Loss + gradients of ONE sample -- or, with `plan` (a `BatchRowsPlan`; `input_ids` / `labels` are then ignored), of one per-device batch laid
+        out as M concatenated rows: `pixel_values` / `image_flags` hold the tiles of all its samples in order.  The ~850 launches of the call all go to the stream that is current at entry: its handle is looked up once and
         pinned for the C-ABI launches (`torch.cuda.current_stream()` per launch was 30 % of the call's host time: tools/micro/sft_host_profile.py); the
         bucket callbacks, which switch streams themselves, run with the pin lifted."""
         with self._on_main():
@@ -460,34 +532,48 @@ class SFTModel(ParamGroup):
                     finally:
                         ops.pin_stream(main)
             try:
-                return self._forward_backward(pixel_values, input_ids, labels, image_flags, on_bucket_ready)
+                return self._forward_backward(pixel_values, input_ids, labels, image_flags, on_bucket_ready, plan)
             finally:
+                self._varlen = None
                 ops.pin_stream(prev)
 
-    def _forward_backward(self, pixel_values, input_ids, labels, image_flags=None, on_bucket_ready=None):
+    def _forward_backward(self, pixel_values, input_ids, labels, image_flags=None, on_bucket_ready=None, plan=None):
         cfg, llm, dev = self.cfg, self.llm, self.device
         v, gv = self.fp.view, self.fp.gview
-        B, S = input_ids.shape
-        if B != 1:
-            raise ValueError('forward_backward takes ONE sample; per-device batches / gradient accumulation go through train_step()')
-        if S > self.S_max:
-            raise ValueError(f'sequence of {S} tokens exceeds max_seq_len={self.S_max}')
-        # index bookkeeping on the HOST copy of the (tiny) id / label tensors -- the collator hands CPU tensors over; CUDA inputs cost
-        # one device->host copy here.  Nothing below reads a device value back, so the whole step is queued without a host sync.
-        ids_h = input_ids.detach().to('cpu', torch.int64).reshape(1, S)
-        lab_h = labels.detach().to('cpu', torch.int64).reshape(-1)
+        if plan is not None:
+            # batch rows: S below is M, the concatenated rows of the batch; every kernel on the path is row-wise except attention (varlen) -- RoPE takes the
+            # angle from `pos`, the K / V cache slot is the global row, the loss is the mean over the batch's R supervised rows
+            S = int(plan.ids.numel())
+            if int((plan.cu_seqlens[1:] - plan.cu_seqlens[:-1]).max()) > self.S_max:
+                raise ValueError(f'a sample of the batch exceeds max_seq_len={self.S_max}')
+            self._grow_rows(S)
+            ids_h, tgt_h, rows_h, R = plan.ids.reshape(1, S), plan.targets, plan.rows, plan.R
+        else:
+            B, S = input_ids.shape
+            if B != 1:
+                raise ValueError('forward_backward takes ONE sample; per-device batches / gradient accumulation go through train_step()')
+            if S > self.S_max:
+                raise ValueError(f'sequence of {S} tokens exceeds max_seq_len={self.S_max}')
+            # index bookkeeping on the HOST copy of the (tiny) id / label tensors -- the collator hands CPU tensors over; CUDA inputs cost
+            # one device->host copy here.  Nothing below reads a device value back, so the whole step is queued without a host sync.
+            ids_h = input_ids.detach().to('cpu', torch.int64).reshape(1, S)
+            lab_h = labels.detach().to('cpu', torch.int64).reshape(-1)
+            tgt_h = torch.full((S,), -100, dtype=torch.int64)
+            tgt_h[:S - 1] = lab_h[1:]                                      # shift: position t predicts token t+1
+            rows_h = (tgt_h != -100).nonzero().flatten()
+            R = int(rows_h.numel())
         if int(ids_h.min()) < 0 or int(ids_h.max()) >= llm.vocab_size:
             raise ValueError(f'input_ids outside [0, {llm.vocab_size})')
-        tgt_h = torch.full((S,), -100, dtype=torch.int64)
-        tgt_h[:S - 1] = lab_h[1:]                                      # shift: position t predicts token t+1
-        rows_h = (tgt_h != -100).nonzero().flatten()
-        R = int(rows_h.numel())
-        n_img = int((ids_h == self.img_context_token_id).sum())
+        n_img = int((ids_h == self.img_context_token_id).sum()) if plan is None else plan.n_img
         H, I, V = llm.hidden_size, llm.intermediate_size, llm.vocab_size
         nq, nkv, hd = llm.num_attention_heads, llm.num_key_value_heads, llm.head_dim
         Lyr = llm.num_hidden_layers
         ids = self._h2d(ids_h)
-        pos = self.pos_all[:S]
+        if plan is not None:
+            pos = self._h2d(plan.pos_ids)
+            self._varlen = (self._h2d(plan.cu_seqlens), plan.cu_seqlens.tolist())
+        else:
+            pos = self.pos_all[:S]
         # ---- vision tower (frozen) + trainable projector (mlp1), with the intermediates mlp1's backward needs
         T = pixel_values.shape[0]
         self._grow_tiles(T)
@@ -631,7 +717,10 @@ class SFTModel(ParamGroup):
             backward.dgrad_nn(dh2, v[f'l{i}.wo'], dao, self.part)
             self._wgrad_side(dh2, ao, gv[f'l{i}.wo'], S, padded=True, ssq=self._ssq(f'l{i}.wo'))
             Kc, VTc = self.cache.k[kslot, 0], self.cache.vt[kslot, 0]         # [nkv, s_max, hd], [nkv, hd, s_max]
-            if self.attn_bwd_mode == 'fused':
+            if self._varlen is not None:
+                ops.attn_bwd_varlen(q, Kc, VTc, ao, dao, self.lse[kslot], self.delta_ws, self.dq[:S], self.dk[:S], self.dv[:S], S, nq, nkv, sm, scale, self._varlen[0],
+                                    head_dim=hd, cu_host=self._varlen[1])
+            elif self.attn_bwd_mode == 'fused':
                 ops.attn_bwd(q, Kc, VTc, ao, dao, self.lse[kslot], self.delta_ws, self.dq[:S], self.dk[:S], self.dv[:S], S, nq, nkv, sm, scale, head_dim=hd)
             else:
                 self._attn_backward(q, Kc, VTc, dao, ao, S, nq, G, hd, sm, scale)
@@ -682,7 +771,7 @@ class SFTModel(ParamGroup):
         QB = self.sc.shape[1]
         nblk = -(-S // QB)
         if nblk > 1 and self.dkv_acc is None:
-            self.dkv_acc = torch.zeros(2, self.S_max, nq * hd, dtype=F32, device=self.device)
+            self.dkv_acc = torch.zeros(2, self.M_max, nq * hd, dtype=F32, device=self.device)
         q1_prev = 0
         for bi in range(nblk):
             q0, q1 = bi * QB, min(S, (bi + 1) * QB)
@@ -852,8 +941,10 @@ class SFTModel(ParamGroup):
         """One optimizer step over `len(micro_batches)` gradient-accumulation micro-batches, each a per-device batch
         `(pixel_values, input_ids [B,S], labels [B,S], image_flags[, attention_mask])` -- the reference launcher's PER_DEVICE_BATCH_SIZE x GRADIENT_ACC
         (…2nd_finetune_full.sh:5-6,49-50).  HF Trainer semantics: each micro-batch's loss is the mean over its supervised tokens,
-        divided by the number of accumulation steps; gradients add up.  The kernels run one sample at a time, so sample b of a
-        micro-batch enters with weight (R_b / R_batch) / n_micro; partial sums live in an fp32 accumulator."""
+        divided by the number of accumulation steps; gradients add up.  By default the kernels run one sample at a time, so sample b of a
+        micro-batch enters with weight (R_b / R_batch) / n_micro; partial sums live in an fp32 accumulator.  With `batch_rows` a micro-batch of B > 1 samples
+        is ONE pass over its concatenated rows (`plan_batch_rows`; varlen attention): its loss is already the mean over the batch's supervised tokens, so it
+        enters with weight 1 / n_micro, and a step of one micro-batch writes every gradient once -- no accumulator, the gradient norm from the producers."""
         if lr is None and total_steps is not None:
             lr = cosine_lr(self.step_count, total_steps, self.lr)
         GA = len(micro_batches)
@@ -866,6 +957,9 @@ class SFTModel(ParamGroup):
                 continue
             smp = self._split_batch(pv, ids, lab, fl, mb[4] if len(mb) > 4 else None)
             Rt = sum(x[4] for x in smp)
+            if self.batch_rows and len(smp) > 1:
+                work.append((pv, None, None, fl, 1.0 / GA, plan_batch_rows(smp, self.img_context_token_id)))
+                continue
             for (pvb, idb, lbb, flb, Rb) in smp:
                 work.append((pvb, idb, lbb, flb, (Rb / Rt if Rt else 0.0) / GA))
         return self._run_weighted(work, lr)
@@ -875,28 +969,36 @@ class SFTModel(ParamGroup):
             return self._run_weighted_main(work, lr)
 
     def _run_weighted_main(self, work, lr):
-        """Samples (pixel_values, ids, labels, image_flags, weight) -> accumulated weighted gradients -> exchange -> optimizer step."""
+        """Samples (pixel_values, ids, labels, image_flags, weight[, BatchRowsPlan]) -> accumulated weighted gradients -> exchange -> optimizer step."""
         self._norm_early = False                   # only trusted when THIS step's backward queued every bucket's partial norm (below)
+        for wk in work:
+            if len(wk) > 5:
+                self._grow_rows(int(wk[5].ids.numel()))
         if len(work) == 1 and work[0][4] == 1.0:
             early = not self.dp_active and self.overlap_optimizer and os.environ.get('VLASER_SFT_NO_EARLY_NORM') != '1'
             self._norm_buckets_seen = 0
             # the norm from the producers (r04) needs every gradient element to be written exactly once by a kernel that can sum it: one sample per step
+            # (or one batch-rows pass: the weight gradients then contract over the M concatenated rows in ONE launch each -- vlaser_gemm_tn_lds never splits its
+            # contraction, and its tile choice, hence the slots it reaches, follows the weight's shape and the CU budget, not the row count)
             # ... and a slot layout that depends on the weight's shape only: true for the LDS-DMA weight-gradient kernel the step takes by default; the A/B fallback
             # (VLASER_SFT_WGRAD=tn) picks its kernel -- and with it the slots it reaches -- by the sequence length, so it keeps the buffer pass
             self._fused_norm = early and self.wgrad_lds and os.environ.get('VLASER_SFT_NO_FUSED_NORM') != '1'
             if self._fused_norm and self.norm_parts is None:
                 self._plan_fused_norm()
             try:
-                loss = self.forward_backward(*work[0][:4], on_bucket_ready=self._norm_bucket if early else self._exchange_bucket)
+                loss = self.forward_backward(*work[0][:4], on_bucket_ready=self._norm_bucket if early else self._exchange_bucket,
+                                             plan=work[0][5] if len(work[0]) > 5 else None)
             finally:
                 self._fused_norm = False
             # a forward_backward that raised never gets here, and one that returned must have signalled every bucket
             self._norm_early = early and self._norm_buckets_seen == len(self.buckets)
         else:
             loss = torch.zeros((), device=self.device)
-            for j, (pvb, idb, lbb, flb, w) in enumerate(work):
+            for j, wk in enumerate(work):
+                pvb, idb, lbb, flb, w = wk[:5]
                 first, last = j == 0, j == len(work) - 1
-                lj = self.forward_backward(pvb, idb, lbb, flb, on_bucket_ready=lambda b, w=w, first=first, last=last: self._accumulate_bucket(b, w, first, last))
+                lj = self.forward_backward(pvb, idb, lbb, flb, on_bucket_ready=lambda b, w=w, first=first, last=last: self._accumulate_bucket(b, w, first, last),
+                                           plan=wk[5] if len(wk) > 5 else None)
                 loss = loss + lj * w
         gnorm = self.optimizer_step(lr)
         return SimpleNamespace(loss=loss, grad_norm=gnorm)
@@ -908,7 +1010,8 @@ class SFTModel(ParamGroup):
         sub-sequences delimited by `cu_seqlens` [B, n+1]; block-diagonal causal attention makes them independent, so each runs as its
         own sample.  The reference's loss sum(w_t ce_t) / sum(w_t) has w constant over the supervised tokens of a sub-sequence
         (`len2weight`, dataset_packed.py:540) and 0 on ignored labels (:622): sub-sequence j therefore enters with weight
-        w_j R_j / sum_k w_k R_k (R = supervised positions)."""
+        w_j R_j / sum_k w_k R_k (R = supervised positions).  `batch_rows` does not change this path: its loss weights are per sub-sequence and the loss
+        kernel (`ce_dlogits`) takes one scalar, so the sub-sequences still run one after another; the varlen kernels are what a batched packed pass will use."""
         if lr is None and total_steps is not None:
             lr = cosine_lr(self.step_count, total_steps, self.lr)
         B, S = input_ids.shape
