@@ -69,7 +69,8 @@ typedef struct {
   /* VL_EPI_SWIGLU, optional: also keep the bf16 pre-activations [M, N] (gate / up in the packed 16-row interleave, exactly what
    * VL_EPI_NONE would write) -- the SFT forward saves them for swiglu's backward instead of running the GEMM unfused + a swiglu pass.
    * VL_EPI_BIAS_GELU, optional (ABI 4): aux_out [M, N] = bf16(acc + bias), the pre-activation GELU's backward needs (the projector's first
-   * Linear, modeling_internvl_chat.py:89-94, was evaluated twice in r02: once with BIAS, once with BIAS_GELU); ld_aux % 4 == 0, 8-byte aligned */
+   * Linear, modeling_internvl_chat.py:89-94, was evaluated twice in r02: once with BIAS, once with BIAS_GELU).
+   * Both: ld_aux % 4 == 0, ld_aux >= N, aux_out 8-byte aligned -- anything else is refused before the launch (as is ldo < N for a row-major out) */
   void* aux_out; int ld_aux;
   /* ABI 5, set by vlaser_gemm_tn_lds only (vlaser_gemm / vlaser_gemm_nn refuse it): see there */
   float* sumsq_part; int sumsq_cap;

@@ -103,6 +103,7 @@ __device__ __forceinline__ void epilogue(const VlaserGemmArgs& a, int m, int n0,
   if constexpr (EPI == VL_EPI_QKV_ROPE) {
     // n0 = head*128 + p where p is the packed in-head row: p = 32*j + 16*half + r  <->  d = 16*j + r + 64*half.
     // v = rows with half 0 (d), v2 = rows with half 1 (d + 64)
+    if (n0 >= a.N) return;      // a 256-column tile past N = heads * 128: such a "head" would land behind the last kv head of the V^T cache
     int head = n0 >> 7;
     int p = n0 & 127;
     int d = ((p >> 5) << 4) + (p & 15);  // p&15 is a multiple of 4; j-th element -> d + j
@@ -148,6 +149,7 @@ __device__ __forceinline__ void epilogue(const VlaserGemmArgs& a, int m, int n0,
   }
   if constexpr (EPI == VL_EPI_VIT_QKV) {
     // columns: [0,C) q, [C,2C) k, [2C,3C) v with C = heads*64 ("three h d", modeling_intern_vit.py:212,231)
+    if (n0 >= a.N) return;      // a 256-column tile past N = 3 C: `which` = 3 would be stored over V^T
     const int C = a.vit_heads * 64;
     int which = n0 / C;
     int c = n0 - which * C;
@@ -1698,6 +1700,14 @@ extern "C" int vlaser_gemm(int epi, const VlaserGemmArgs* a, vl_stream_t s) {
            "vlaser_gemm: force_bm must be 0/32/64/128 or an LDS-DMA configuration code 1100/1105/1200/1300/1301/1440/1500/1506/1532/1564/1900, 2100 (lab: producer waves)");
   VL_CHECK(a->lda % 8 == 0 && a->ldw % 8 == 0, "vlaser_gemm: lda/ldw must be multiples of 8 (16-byte rows)");
   VL_CHECK(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->W & 15) == 0, "vlaser_gemm: operands must be 16-byte aligned");
+  // the row-major bf16 / fp32 output (and the residual read with its stride): rows must not overlap -- the epilogues bound their stores by N, not by ldo
+  if (epi == VL_EPI_NONE || epi == VL_EPI_F32 || epi == VL_EPI_BIAS || epi == VL_EPI_BIAS_GELU || epi == VL_EPI_BIAS_LS_RES || epi == VL_EPI_RES)
+    VL_CHECK(a->ldo >= a->N, "vlaser_gemm: ldo=%d is smaller than N=%d", a->ldo, a->N);
+  if (epi == VL_EPI_SWIGLU) VL_CHECK(a->ldo >= a->N / 2, "vlaser_gemm: swiglu: ldo=%d is smaller than N/2=%d", a->ldo, a->N / 2);
+  // aux_out rows are written with 8-byte stores at columns that are multiples of 4 (epilogue_tile, epilogue<VL_EPI_SWIGLU>)
+  if ((epi == VL_EPI_BIAS_GELU || epi == VL_EPI_SWIGLU) && a->aux_out)
+    VL_CHECK(a->ld_aux % 4 == 0 && a->ld_aux >= a->N && ((uintptr_t)a->aux_out & 7) == 0,
+             "vlaser_gemm: aux_out must be 8-byte aligned with ld_aux a multiple of 4 and >= N (ld_aux=%d, N=%d)", a->ld_aux, a->N);
   switch (epi) {
     case VL_EPI_NONE: VL_CHECK(a->out, "out null"); return launch<VL_EPI_NONE>(a, stream);
     case VL_EPI_F32: VL_CHECK(a->out, "out null"); return launch<VL_EPI_F32>(a, stream);
