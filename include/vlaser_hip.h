@@ -239,7 +239,8 @@ int vlaser_chain_down2(const void* x, int ldx, const void* W, float* out_f32, in
  *   dK, dV:  one workgroup per (64 keys, q head) walks the query tiles that see them: S, P, dP, dS, dV^T += dO^T P, dK^T += Q^T dS
  * q / o / d_o / dq: bf16 [S, n_q*128]; k: [n_kv, s_max, 128] (post-RoPE), vt: [n_kv, 128, s_max]; lse: fp32 [n_q, S] from vlaser_attn_prefill;
  * dk / dv: bf16 [S, n_q*128] -- ONE partial per Q head (vlaser_rope_bwd_pack sums the heads of a kv group); delta_ws: fp32 [n_q, S] scratch.
- * Key k is visible to query q iff k < kv_valid and (k <= q when causal != 0).  head_dim 128. */
+ * Key k is visible to query q iff k < kv_valid and (k <= q when causal != 0).  head_dim 128.  1 <= kv_valid <= s_max; causal: a kv_valid above S means S;
+ * non-causal: kv_valid > S is refused (dk / dv have S rows: dQ would sum over keys that have no gradient row). */
 int vlaser_attn_bwd(const void* q, const void* k, const void* vt, const void* o, const void* d_o, const float* lse, float* delta_ws, void* dq, void* dk,
                     void* dv, int S, int n_q, int n_kv, int s_max, float scale, int causal, int kv_valid, int head_dim /* 128, checked */, vl_stream_t stream);
 /* (ABI 8, varlen) The backward of vlaser_attn_varlen (flash_attn_varlen_func's autograd, qwen2_packed_training_patch.py:71-96; the padded batch's causal
@@ -255,6 +256,8 @@ int vlaser_attn_bwd_varlen(const void* q, const void* k, const void* vt, const v
 /* Weight-gradient GEMM: out[M,N] (bf16) = At^T @ Wt, At [K,M] and Wt [K,N] row-major bf16 (contraction along rows).
  * dW = dY^T X of every nn.Linear on the SFT path (autograd of modeling_internvl_chat.py:194-203): At = dY [S,N_out],
  * Wt = X [S,K_in].  Rows 16-byte aligned and readable up to M / N rounded up to 8 columns (ld >= that).
+ * out: ldo >= N; with ldo % 4 == 0 its rows are stored in 8-byte pieces, so `out` must be 8-byte aligned (and o_bs of the grouped form a multiple of 4) --
+ * anything else is refused; an ldo that is no multiple of 4 takes element stores and needs no alignment.
  * sumsq_part (ABI 5, optional, NULL = off): float[sumsq_cap]; every (workgroup, wave) of the launch writes the sum of the squares of the bf16 values it
  * stored into its own slot (slots the launch does not reach are left untouched; which slots it reaches depends on M, N only).  The caller adds the
  * slots in index order (vlaser_sum_partials): the weight gradient's share of clip_grad_norm_'s global norm (internvl_chat_finetune.py:1041-1057,

@@ -27,12 +27,11 @@ import math
 import pytest
 import torch
 
-from bounds import BF, D64, FLOOR, LN_KINDS, SENT, U, ULP, _ln_rows, bits, bound, h64, sentinel
-from parity import parity
+from bounds import (BF, D64, F32, FLOOR, LN_KINDS, SENT, U, ULP, Worst, _ln_rows, bits, bound, dev, dev_off, f32s, h64, is_sent, pow2, randb, rbf, same_bits,
+                    sentinel)
 
 pytestmark = pytest.mark.gpu
 LOG2E = 1.4426950408889634
-F32 = torch.float32
 
 
 @pytest.fixture(scope='module')
@@ -49,74 +48,8 @@ def _grad_off():
 
 
 # ------------------------------------------------------------------------------------------------ helpers
-def pow2(n, lo=-10, hi=2):
-    """2^e with e cycling over lo .. hi"""
-    return 2.0 ** ((torch.arange(n) % (hi - lo + 1)) + lo).float()
-
-
-def randb(*shape, seed=0, std=1.0):
-    """bf16-valued fp32 CPU tensor"""
-    g = torch.Generator().manual_seed(seed + 7 * sum(shape))
-    return (torch.randn(*shape, generator=g) * std).to(BF).float()
-
-
-def dev(t, dtype=BF):
-    return t.to(dtype).cuda().contiguous()
-
-
-def dev_off(t):
-    """device bf16 copy that starts 2 bytes past an aligned address"""
-    buf = sentinel(t.numel() + 8)
-    buf[1:1 + t.numel()] = t.flatten().to(BF).cuda()
-    return buf[1:1 + t.numel()].view(t.shape)
-
-
-def f32s(x):
-    """a Python scalar as the C ABI's float argument holds it"""
-    return float(torch.tensor(x, dtype=F32))
-
-
 def gelu64(z):
     return 0.5 * z * torch.special.erfc(-z / math.sqrt(2))
-
-
-def rbf(t):
-    """round an fp64 tensor to bf16 (through fp32: a double rounding only on exact fp32 ties of fp64 data, which these products of bf16 values never hit)"""
-    return t.to(F32).to(BF).to(D64)
-
-
-def same_bits(a, b):
-    it = torch.int32 if a.dtype == F32 else torch.int16
-    return torch.equal(a.contiguous().view(it), b.contiguous().view(it))
-
-
-def is_sent(t):
-    return bool((t == SENT).all())
-
-
-class Worst:
-    """worst |got - ref| / tol over the cases of one test, logged once per name (with the case that gave it)"""
-
-    def __init__(self):
-        self.figs = {}
-
-    def add(self, name, got, ref, tol, where=''):
-        got = h64(got)
-        assert torch.isfinite(got).all(), f'{name} {where}: non-finite output'
-        assert got.shape == ref.shape, (name, where, got.shape, ref.shape)
-        f = ((got - ref).abs() / tol).max().item() if got.numel() else 0.0
-        if name not in self.figs or f > self.figs[name][0]:
-            self.figs[name] = (f, where)
-        return f
-
-    def flush(self):
-        bad = []
-        for name, (f, where) in self.figs.items():
-            try:
-                parity(name, f, 1.0, note=f'max |got - ref| / tol at {where}')
-            except AssertionError as e:
-                bad.append(str(e))
-        assert not bad, '\n'.join(bad)
 
 
 # ================================================================================================ A. vlaser_gemm epilogues at the edges of epilogue_tile

@@ -433,10 +433,12 @@ extern "C" int vlaser_attn_bwd(const void* q, const void* k, const void* vt, con
   VL_CHECK(q && k && vt && o && d_o && lse && delta_ws && dq && dk && dv, "vlaser_attn_bwd: null pointer");
   VL_CHECK(head_dim == 128, "vlaser_attn_bwd: head_dim %d -- the kernels are built for head_dim 128 (Qwen2.5)", head_dim);
   VL_CHECK(S >= 1 && n_q % n_kv == 0 && s_max % 64 == 0 && S <= s_max && kv_valid >= 1 && kv_valid <= s_max, "vlaser_attn_bwd: bad geometry");
+  // keys live on the S rows of dk / dv: a non-causal prefix longer than S would let dQ sum over keys whose dK / dV rows do not exist (causal: clamped to S below)
+  VL_CHECK(causal || kv_valid <= S, "vlaser_attn_bwd: non-causal kv_valid %d exceeds the %d rows of dk / dv", kv_valid, S);
   AttnBwdP p;
   p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.vt = (const bf16_t*)vt; p.o = (const bf16_t*)o; p.d_o = (const bf16_t*)d_o;
   p.lse = lse; p.delta = delta_ws; p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
-  p.S = S; p.n_q = n_q; p.n_kv = n_kv; p.s_max = s_max; p.scale = scale; p.causal = causal; p.kv_valid = kv_valid < S ? kv_valid : (causal ? S : kv_valid);
+  p.S = S; p.n_q = n_q; p.n_kv = n_kv; p.s_max = s_max; p.scale = scale; p.causal = causal; p.kv_valid = kv_valid < S ? kv_valid : S;
   const dim3 grid((S + 63) / 64, n_q);
   static const int force_ks = getenv("VLASER_ATTN_BWD_KS") ? atoi(getenv("VLASER_ATTN_BWD_KS")) : 0;       // tuning / A-B
   const int ks = force_ks == 1 || force_ks == 2 ? force_ks : (S > 128 ? 2 : 1);

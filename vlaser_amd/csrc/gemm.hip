@@ -1635,6 +1635,10 @@ static int gemm_tn_launch(const void* At, const void* Wt, void* out, int M, int 
   VL_CHECK(ldat % 8 == 0 && ldwt % 8 == 0 && (((uintptr_t)At | (uintptr_t)Wt) & 15) == 0 && ((a_gs | w_gs | a_bs | w_bs) & 7) == 0,
            "vlaser_gemm_tn: operands must be 16-byte aligned rows / group / batch strides");
   VL_CHECK(ldat >= ((M + 7) & ~7) && ldwt >= ((N + 7) & ~7), "vlaser_gemm_tn: operand rows must be readable up to M, N rounded up to 8 columns");
+  // rows of `out` are stored in 8-byte pieces when ldo % 4 == 0 (element by element otherwise): every row of every batch element must then start 8-byte aligned
+  VL_CHECK(ldo >= N, "vlaser_gemm_tn: ldo=%d is smaller than N=%d", ldo, N);
+  VL_CHECK((ldo & 3) != 0 || ((((uintptr_t)out) & 7) == 0 && (o_bs & 3) == 0),
+           "vlaser_gemm_tn: with ldo %% 4 == 0 the rows of out are stored in 8-byte pieces: out must be 8-byte aligned and o_bs a multiple of 4");
   GemmTnP p{(const bf16_t*)At, (const bf16_t*)Wt, (bf16_t*)out, M, N, K, ldat, ldwt, ldo, 0, (N + BN - 1) / BN, groups, a_gs, w_gs, a_bs, w_bs, o_bs, sumsq_part};
   hipStream_t stream = reinterpret_cast<hipStream_t>(s);
   constexpr int lds64 = 2 * (64 * (64 * 2 + 32) + 64 * (BN * 2 + 32)), lds128 = 2 * (64 * (128 * 2 + 32) + 64 * (BN * 2 + 32));
