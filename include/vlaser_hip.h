@@ -476,8 +476,8 @@ int vlaser_attn_rows_bwd(const void* q, const void* K, const void* VT, const voi
 /* softmax + dS of an attention backward through materialised score matrices, in one pass: P = softmax(scale * scores) over the visible keys (bf16),
  * dS = P o (dP - D) * scale with D[q] = sum_d dO[q,d] O[q,d]; scores, dP fp32 [H, S, ld]; dO, O bf16 [S, H*hd]; P, dS bf16 [H, S, ld] (0 on masked keys).
  * Key k is visible to query row q iff k < kv_valid and (k <= q + q_off when causal != 0); q_off = global index of row 0 when the S rows are a block
- * of a longer sequence (`VLASER_SFT_ATTN_BWD=materialised` walks the queries in blocks: the score matrices stay [heads, block, keys]).  On the default
- * path this serves the bidirectional valid-prefix / full masks of the VLM group (vla_vlm_group.py); the causal SFT attention uses vlaser_attn_bwd. */
+ * of a longer sequence (`SFTModel(attn_bwd='materialised')` walks the queries in blocks: the score matrices stay [heads, block, keys]).  On the default
+ * path this serves the full mask of the VLM group's vision tower (vla_vlm_group.py); the causal SFT attention uses vlaser_attn_bwd. */
 int vlaser_attn_bwd_pds_masked(const float* scores, const float* dP, const void* dO, const void* O, void* P, void* dS, int n_heads, int S, int ld, int hd,
                                float scale, int causal, int kv_valid, int q_off, vl_stream_t stream);
 /* vlaser_attn_rows_bwd that also stores P and dS of EVERY key, bf16 [n_q][16][s_max] (row r of head h at (h*16 + r)*s_max): the prefix keys' dK / dV

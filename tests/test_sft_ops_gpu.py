@@ -772,7 +772,6 @@ def _adamw_blocks(n, cap):
 
 
 def _adamw_cap(ops):
-    assert not os.environ.get('VLASER_ADAMW_BLOCKS')
     return min(ops.get_cu_budget(), torch.cuda.get_device_properties(0).multi_processor_count)
 
 

@@ -1,6 +1,6 @@
 """In-kernel timeline of attn_bwd_dq_kernel (lab build with -DAB_TIMELINE: tools/micro/lab_build/libvlaser_abtl.so, see the header of this script's
 build line in profiles/): cycle stamps of wave 0 of the last query tile (longest key chain) at S = 560.
-    VLASER_HIP_LIB=$PWD/tools/micro/lab_build/libvlaser_abtl.so [VLASER_ATTN_BWD_KS=1|2] python tools/micro/attn_bwd_timeline.py"""
+    VLASER_HIP_LIB=$PWD/tools/micro/lab_build/libvlaser_abtl.so python tools/micro/attn_bwd_timeline.py"""
 import ctypes as C
 import os
 import sys

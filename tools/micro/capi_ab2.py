@@ -46,8 +46,6 @@ print('| forward + backward, cu budget %d | ms |\n|---|---|' % ops.get_cu_budget
 timed('main masked (per-call switch), wgrad masked')
 m.wgrad_stream = plain_wg
 timed('main masked (per-call switch), wgrad on a plain stream')
-m.wgrad_stream = None
-timed('main masked (per-call switch), no wgrad stream')
 m.main_stream = None
 m.wgrad_stream = masked_wg
 timed('caller on the default stream (no main mask), wgrad masked')

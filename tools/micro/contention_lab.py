@@ -61,7 +61,7 @@ sm = 576
 q = rnd(S, nq * hd, std=1.0); Kc = rnd(1, nkv, sm, hd, std=1.0); vt = rnd(1, nkv, hd, sm, std=1.0)
 ao = torch.zeros(S, nq * hd, dtype=BF, device=dev)
 lse = torch.zeros(nq * S, dtype=F32, device=dev)
-row(f'attention causal S=560 (KS={os.environ.get("VLASER_ATTN_KS", "auto")})', lambda c: [lambda: ops.attn_prefill(q, Kc, vt, ao, 1, S, S, nq, nkv, hd, (S * nq * hd, hd, nq * hd), (nkv * sm * hd, sm * hd),
+row('attention causal S=560', lambda c: [lambda: ops.attn_prefill(q, Kc, vt, ao, 1, S, S, nq, nkv, hd, (S * nq * hd, hd, nq * hd), (nkv * sm * hd, sm * hd),
             (nkv * hd * sm, hd * sm), (S * nq * hd, nq * hd), sm, hd ** -0.5, L.ATTN_CAUSAL, lse_out=lse)] * 4)
 wo = [rnd(H, nq * hd) for _ in range(4)]
 part = torch.zeros(8 * S * H, dtype=F32, device=dev)

@@ -71,8 +71,7 @@ def main():
         ops.set_cu_budget(budget)
         main = masked(0, budget) if 'c' in masks else torch.cuda.current_stream()
         side_ = masked(budget, 256 - budget) if 's' in masks else side
-        if model.wgrad_stream is not None:            # the weight gradients' side stream gets the compute mask too
-            model.wgrad_stream = masked(0, budget, 1) if 'c' in masks else wgrad0
+        model.wgrad_stream = masked(0, budget, 1) if 'c' in masks else wgrad0            # the weight gradients' side stream gets the compute mask too
         with torch.cuda.stream(main):
             for _ in range(2):                        # (tile choices are made per launch; warm the variant's code objects)
                 model.forward_backward(pv, ids, labels)

@@ -18,8 +18,6 @@
 //   CAUSAL : lim1 = min(kv_len, i + 1 + causal_off)
 //   PREFIX : lim1 = valid_len[b]; rows >= blk_start additionally see [blk_start, kv_len)
 //   VARLEN : (vlaser_attn_varlen) n sequences back to back, row i of sequence [lo, hi) sees lo <= j <= i
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 #include "common.h"
 #include "../../include/vlaser_hip.h"
@@ -717,27 +715,22 @@ extern "C" int vlaser_attn_prefill(const VlaserAttnArgs* a, vl_stream_t s) {
     VL_LAUNCH_CHECK();
     return 0;
   }
-  // tile / split choice, measured (tools/micro/attn_lab.py, profiles/r02k_attn.md): a 2-way in-workgroup key split pays only when
+  // tile / split choice, measured (profiles/r02k_attn.md): a 2-way in-workgroup key split pays only when
   // the grid does not even reach one workgroup per CU (joint prefill: 72 workgroups, 11.4 -> 10.8 us); 128-key tiles only for the
   // unmasked head_dim-64 case around one workgroup per CU (ViT, 1 tile: 23.9 -> 22.8 us); more registers per wave (a forced
   // 4 waves / SIMD) and a 4-way split both lose everywhere
   const long blocks = (long)grid.x * grid.y * grid.z;
-  static const int force_ks = getenv("VLASER_ATTN_KS") ? atoi(getenv("VLASER_ATTN_KS")) : 0;      // tuning / A-B
   // r03: the split is 8 % faster alone at 108 workgroups (S = 560: 14.7 vs 15.9 us) but stretches x2.5 instead of x1.5 when the SFT step's AdamW streams
   // beside it (tools/micro/contention_lab.py; whole step 23.4 -> 22.8 ms with the split off): only grids below 96 workgroups split
-  int ks = force_ks == 1 || force_ks == 2 ? force_ks : (blocks <= 96 ? 2 : 1);
+  int ks = blocks <= 96 ? 2 : 1;
   const int tk = (a->head_dim == 64 && a->mode == VL_ATTN_FULL && blocks <= 512 && ks == 1) ? 128 : 64;
   if (a->kv_len <= tk) ks = 1;
-  static const int no_tail = getenv("VLASER_ATTN_NO_TAIL") ? atoi(getenv("VLASER_ATTN_NO_TAIL")) : 0;                       // A/B: the r03 schedule
-  if (a->mode == VL_ATTN_FULL && !no_tail && ks == 1) {      // (the 2-way key-split variant at head_dim 128 has no registers to spare for the tail chunk)
+  if (a->mode == VL_ATTN_FULL && ks == 1) {      // (the 2-way key-split variant at head_dim 128 has no registers to spare for the tail chunk)
     const int tail = a->kv_len % tk;
     if (tail >= 1 && tail <= 32 && a->kv_len > tk) p.tail_key0 = a->kv_len - tail;
     if (a->sq % 64 >= 1 && a->sq % 64 <= 16 && a->sq > 64) p.tail_qb = a->sq / 64;
-    static const int tail_wg = getenv("VLASER_ATTN_TAIL_WG") ? atoi(getenv("VLASER_ATTN_TAIL_WG")) : 0;                     // A/B: the tail rows in workgroups of their own (first r04 form)
-    if (p.tail_qb >= 0 && !tail_wg && tk == 128) p.tail_host = 1;          // the one-round grids (tk == 128 <=> <= 512 workgroups); larger grids keep the tail workgroups
+    if (p.tail_qb >= 0 && tk == 128) p.tail_host = 1;          // the one-round grids (tk == 128 <=> <= 512 workgroups); larger grids keep the tail workgroups
   }
-  static const int dbg_attn = getenv("VLASER_ATTN_DEBUG") ? 1 : 0;
-  if (dbg_attn) fprintf(stderr, "attn_prefill: sq %d kv %d hd %d mode %d blocks %ld ks %d tk %d tail_key0 %d tail_qb %d\n", a->sq, a->kv_len, a->head_dim, a->mode, blocks, ks, tk, p.tail_key0, p.tail_qb);
 #define VL_ATTN_LAUNCH(HD_, KS_, TK_)                                                                                       \
   do {                                                                                                                      \
     constexpr int tile = 2 * TK_ * HD_ * 2, merge = (KS_ - 1) * 4 * (HD_ / 16 * 4 + 2) * 256;                                \

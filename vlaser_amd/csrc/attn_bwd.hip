@@ -440,8 +440,7 @@ extern "C" int vlaser_attn_bwd(const void* q, const void* k, const void* vt, con
   p.lse = lse; p.delta = delta_ws; p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
   p.S = S; p.n_q = n_q; p.n_kv = n_kv; p.s_max = s_max; p.scale = scale; p.causal = causal; p.kv_valid = kv_valid < S ? kv_valid : S;
   const dim3 grid((S + 63) / 64, n_q);
-  static const int force_ks = getenv("VLASER_ATTN_BWD_KS") ? atoi(getenv("VLASER_ATTN_BWD_KS")) : 0;       // tuning / A-B
-  const int ks = force_ks == 1 || force_ks == 2 ? force_ks : (S > 128 ? 2 : 1);
+  const int ks = S > 128 ? 2 : 1;
   static const bool two_launches = getenv("VLASER_ATTN_BWD_TWO_LAUNCHES") && atoi(getenv("VLASER_ATTN_BWD_TWO_LAUNCHES")) == 1;      // A/B: the r03 form
 #define AB_LAUNCH(KS_)                                                                                               \
   {                                                                                                                  \

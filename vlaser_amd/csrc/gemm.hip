@@ -11,9 +11,6 @@
 // ds_read_b128.  Global->register prefetch of tile k+1 overlaps the MFMAs of tile k; one barrier per K-step.
 // blockIdx is remapped so each XCD owns a contiguous run of tiles that share the same weight panel (guide T1).
 
-#include <cstdlib>
-#include <cstring>
-#include <cstdio>
 #include "common.h"
 #include "../../include/vlaser_hip.h"
 
@@ -1345,10 +1342,7 @@ static int launch(const VlaserGemmArgs* args, hipStream_t stream) {
       // r04: grids of more than one round take the staggered two-group kernel (gate/up 46.0 -> 43.8 us; single-round shapes tie: tools/micro/gemm_epilogue_lab.py)
       if (blocks(128, 128) <= cus) bm = 1100;
       else if (blocks(128, 256) <= cus) bm = 1200;
-      else {
-        static const bool no_stag = getenv("VLASER_TN_NO_STAG") != nullptr;      // diagnostics / same-box A/B: the plain two-stage 256x256 ring for multi-round grids too
-        bm = (EPI == VL_EPI_NONE && nb == 1 && blocks(256, 256) > cus && !no_stag) ? 1340 : 1300;
-      }
+      else bm = (EPI == VL_EPI_NONE && nb == 1 && blocks(256, 256) > cus) ? 1340 : 1300;
     } else if (args->M <= 32 && !WKM) {
       bm = 32;
     } else if (!WKM && blocks(64, 64) <= cus) {      // (the NN form's transposing reads need >= 16 slots per staged k-row: BNT >= 128)
@@ -1375,24 +1369,6 @@ static int launch(const VlaserGemmArgs* args, hipStream_t stream) {
     }
   }
   // LDS-DMA pipeline configurations: 1100 = 128x128 / 4 stages, 1200 = 128x256 / 3, 1300 = 256x256 / 2, 1500 = 64x128 / 4 (8 waves each), 1440 = 144x128 / 4 (6 waves)
-  if constexpr (!AKM) {
-    static const bool no_asym = getenv("VLASER_GEMM_NO_ASYM") != nullptr;      // diagnostics / same-box A/B: the r03-r04 two-stage rings instead of the asymmetric ones
-    if (no_asym) bm = bm == 1900 ? 1901 : bm == 1300 ? 1302 : bm;
-  }
-  if constexpr (!AKM) {
-    // diagnostics / same-box A/B: the refill as one burst per K-step (r02-r04) -- "1" for every configuration, or a list of configuration codes ("1200,1500")
-    static const char* no_spread = getenv("VLASER_GEMM_NO_SPREAD");
-    if (no_spread) {
-      char code[8];
-      snprintf(code, sizeof(code), "%d", bm);
-      if (!strcmp(no_spread, "1") || strstr(no_spread, code))
-        bm = bm == 1100 ? 1101 : bm == 1200 ? 1201 : bm == 1300 ? 1304 : bm == 1440 ? 1441 : bm == 1500 ? 1501 : bm == 1900 ? 1904 : bm;      // (burst forms: plain loops)
-    }
-  }
-  {
-    static const bool no_pipe = getenv("VLASER_GEMM_NO_PIPE") != nullptr;      // diagnostics / same-box A/B: the r05 plain K loop on the tiles that pipeline their fragment reads
-    if (no_pipe) bm = bm == 1440 ? 1442 : bm == 1500 ? 1502 : bm == 1564 ? 1566 : bm == 1900 ? 1902 : bm;
-  }
   if constexpr (AKM) {
     switch (bm) {
       // (r05: neither the asymmetric ring nor the spread refill helps the TN form -- both operands are activations / gradients out of L2, and its 256x256 tile lost 3-6 % with
@@ -1414,10 +1390,10 @@ static int launch(const VlaserGemmArgs* args, hipStream_t stream) {
   }
   switch (bm) {
     // r05: the refill's pieces go out one at a time between the K-step's MFMAs (SPREAD: bit-identical, -1 ... -9 % per launch, tools/micro/spread_lab.py); 1101 / 1201 / 1304 / 1441 /
-    // 1501 / 1904 = the burst forms of r02-r04 (lab, VLASER_GEMM_NO_SPREAD=1)
+    // 1501 / 1904 = the burst forms of r02-r04 (lab, through force_bm)
     // r06: fragment reads pipelined across the K-step's barrier (PIPE: bit-identical; whole launches -4.1 ... -5.0 % on 144x128, -2.5 ... -5.3 % on 64x128, -6.1 ... -6.3 % on 64x64,
     // -4.3 ... -6.6 % on 192x256, noise on 128x128 / 128x256 which keep the plain loop -- profiles/r06o_pipe_ab.md); 1442 / 1502 / 1566 / 1902 = the r05 defaults for same-box A/B
-    // (VLASER_GEMM_NO_PIPE=1)
+    // (through force_bm)
     case 1100: return launch_glds<EPI, 128, 128, 2, 4, 4, WKM, false, false, 0, false, true>(args, stream, splits);
     case 1110: return launch_glds<EPI, 128, 128, 2, 4, 4, WKM, false, false, 0, false, true, true>(args, stream, splits);      // lab: PIPE on 128x128 (-2.4 ... +3.6 %: noise; not the default)
     case 1101: return launch_glds<EPI, 128, 128, 2, 4, 4, WKM>(args, stream, splits);

@@ -10,8 +10,6 @@ Weights are stored in HBM in the layouts the kernels want (packed once at load):
   * K cache [L][B,n_kv,S_max,128], V cache TRANSPOSED [L][B,n_kv,128,S_max] (MFMA A-fragment = one 16-byte load).
 """
 
-import os
-
 import torch
 from types import SimpleNamespace
 
@@ -224,7 +222,7 @@ def residual_seam(a, w, h, part, M, N, K, x_out=None, bias=None, ls=None, norm=0
         the fp32 summation order.  (The one-tile ViT proj, 2 slabs of 1025 rows, is 3 us faster as a pair in isolation and EQUAL inside the chunk -- same-box A/B 11.775 vs
         11.778 ms -- so the small shapes keep the slab path and their bit-exact history.)"""
     sp = ops.gemm_splits(M, N, K, part.numel()) if splits is None else splits
-    if sp >= 3 or (sp == 2 and M < 2048) or os.environ.get('VLASER_SEAM_SPLITK') == '1':
+    if sp >= 3 or (sp == 2 and M < 2048):
         ops.gemm(L.EPI_PARTIAL, a, w, out_f32=part, k_splits=sp)
         ops.reduce_norm(h, part, sp, M, N, h, x_out, bias=bias, ls=ls, norm=norm if x_out is not None else 0, norm_w=norm_w, norm_b=norm_b, eps=eps)
         return

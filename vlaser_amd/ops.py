@@ -2,7 +2,6 @@
 memory and the stream; every op below is a launch of a hand-written gfx950 kernel in libvlaser_hip.so."""
 import ctypes as C
 import math
-import os
 
 
 import threading
@@ -704,7 +703,7 @@ def split_slab_elems(max_rows, N):
 _GEMM_STEP_US = {32: (5.0, 0.30), 1564: (4.9, 0.177), 1500: (5.1, 0.263), 1100: (5.3, 0.377), 1440: (5.6, 0.509), 1200: (7.0, 0.62), 1300: (9.0, 1.55), 1900: (8.5, 1.2)}
 
 
-_SPLIT_MIN_K = int(os.environ.get('VLASER_GEMM_SPLIT_MINK', '512'))      # >= 8 K-steps per slice: the fitted model does not extrapolate to shorter loops
+_SPLIT_MIN_K = 512      # >= 8 K-steps per slice: the fitted model does not extrapolate to shorter loops
 
 
 def gemm_splits(M, N, K, max_elems=None, max_splits=8, nn=False):
@@ -759,9 +758,6 @@ def avg_update(avg, p, c, first):
 
 
 # ------------------------------------------------------------------------------------------------ SFT (backward / optimizer)
-_TN_LDS = os.environ.get('VLASER_TN_LDS', '1') == '1'
-
-
 def _ssq(part):
     """(pointer, capacity) of an optional fp32 slot array for the per-wave sums of squares a weight-gradient GEMM leaves behind."""
     if part is None:
@@ -776,7 +772,7 @@ def gemm_tn(At, Wt, out, K=None, sumsq_part=None):
     M, N = At.shape[1], Wt.shape[1]
     c8 = lambda n: (n + 7) // 8 * 8
     if K % 64 == 0 and At.stride(0) >= c8(M) and Wt.stride(0) >= c8(N) and At.stride(0) % 8 == 0 and Wt.stride(0) % 8 == 0 \
-            and (At.data_ptr() | Wt.data_ptr()) % 16 == 0 and M * N >= 128 * 128 and _TN_LDS:       # ragged M / N: rows must be readable up to the next multiple of 8
+            and (At.data_ptr() | Wt.data_ptr()) % 16 == 0 and M * N >= 128 * 128:       # ragged M / N: rows must be readable up to the next multiple of 8
         return gemm_tn_lds(At, Wt, out, K, sumsq_part=sumsq_part)          # whole 64-row tiles: nothing to pad, the LDS-DMA pipeline applies as is
     sp, cap = _ssq(sumsq_part)
     L.check(L.lib().vlaser_gemm_tn(At.data_ptr(), Wt.data_ptr(), out.data_ptr(), M, N, K, At.stride(0), Wt.stride(0), out.stride(0), sp, cap, _stream()),

@@ -152,11 +152,10 @@ class SFTModel(ParamGroup):
         # the attention backward walks the query rows in blocks of this many (r03): its score matrices are [heads, block, keys], not [heads, S, S] --
         # the reference's launcher trains at --max_seq_length 16384 (…2nd_finetune_full.sh:38,60), where four S x S matrices per head are 38 GB
         self.attn_bwd_block = attn_bwd_block
-        self.wgrad_lds = os.environ.get('VLASER_SFT_WGRAD', 'lds') == 'lds'      # 'tn': the register-staged TN kernel everywhere (A/B)
         self._wgrad_pad_S = None
-        self.attn_bwd_mode = os.environ.get('VLASER_SFT_ATTN_BWD', attn_bwd)
+        self.attn_bwd_mode = attn_bwd
         if self.attn_bwd_mode not in ('fused', 'materialised'):
-            raise ValueError(f'VLASER_SFT_ATTN_BWD={self.attn_bwd_mode!r}: fused | materialised')
+            raise ValueError(f'attn_bwd={self.attn_bwd_mode!r}: fused | materialised')
         # batch_rows (VLASER_SFT_BATCH_ROWS=1): a micro-batch of B > 1 samples runs as ONE forward / backward over its concatenated rows (varlen attention,
         # csrc/attn.hip + attn_bwd.hip `VARLEN`) instead of B passes of one sample each.  Off by default: the one-sample path is unchanged bit for bit.
         env_br = os.environ.get('VLASER_SFT_BATCH_ROWS')
@@ -172,8 +171,6 @@ class SFTModel(ParamGroup):
         self.norm_parts = None
         self._embed_touched = None
         self._head_pad_Rp = None
-        self.overlap_allgather = os.environ.get('VLASER_SFT_NO_AG_OVERLAP') != '1'
-        self.overlap_optimizer = os.environ.get('VLASER_SFT_NO_OPT_OVERLAP') != '1'
         self.step_count = 0
         self.img_context_token_id = cfg.img_context_token_id
         self.max_tiles = max_tiles
@@ -238,7 +235,7 @@ class SFTModel(ParamGroup):
         self.dao, self.dq, self.dk, self.dv = z(S, nq * hd), z(S, nq * hd), z(S, nq * hd), z(S, nq * hd)      # dk / dv: one partial per Q head
         self.dqkv = z(S, NQ)
         G = nq // nkv
-        # attention backward: fused (csrc/attn_bwd.hip: the forward keeps the log-sum-exp, no score matrices) or, VLASER_SFT_ATTN_BWD=materialised,
+        # attention backward: fused (csrc/attn_bwd.hip: the forward keeps the log-sum-exp, no score matrices) or, attn_bwd='materialised',
         # the r02 path through [heads, rows, keys] score matrices, one block of attn_bwd_block query rows at a time
         self.lse = torch.zeros(Lk, nq * S, dtype=F32, device=dev)
         self.delta_ws = torch.zeros(nq * S, dtype=F32, device=dev)
@@ -252,9 +249,9 @@ class SFTModel(ParamGroup):
         self.sumsq_ws = torch.zeros(1024, dtype=F32, device=dev)
         self.normw_ws = torch.zeros((S + 3) // 4 * H, dtype=F32, device=dev)      # norm-weight gradient partials of rmsnorm_bwd
         # r04: the two norm-weight gradients of every layer of a bucket leave their partials in slots of their own and are finished by ONE launch when the
-        # bucket completes (2 x bucket_layers launches less per bucket; `VLASER_SFT_NO_NORMW_BATCH=1`: A/B)
+        # bucket completes (2 x bucket_layers launches less per bucket)
         self.normw_slot = (S + 3) // 4 * H
-        self.normw_multi = None if os.environ.get('VLASER_SFT_NO_NORMW_BATCH') == '1' else torch.zeros(2 * self.bucket_layers * self.normw_slot, dtype=F32, device=dev)
+        self.normw_multi = torch.zeros(2 * self.bucket_layers * self.normw_slot, dtype=F32, device=dev)
         self._normw_off = {}                    # first layer of a bucket -> device int64 offsets of its ln_post / ln_in gradients in fp.g, in slot order
         self.gnorm2 = torch.zeros(1, dtype=F32, device=dev)
         self.rank_ws = torch.zeros(S, dtype=torch.int32, device=dev)
@@ -298,14 +295,13 @@ class SFTModel(ParamGroup):
                 ops.set_cu_budget(mask[1])
         else:
             self.comm_stream = torch.cuda.Stream(device=dev) if self.dp_active else None
-        mk = (lambda **kw: rccl_capi.masked_stream(*mask)) if mask is not None else (lambda **kw: torch.cuda.Stream(device=dev, **kw))
+        mk = (lambda: rccl_capi.masked_stream(*mask)) if mask is not None else (lambda: torch.cuda.Stream(device=dev))
         # single rank: AdamW (HBM-bound, a third of a step) runs on its own stream bucket by bucket in the order the next forward
         # consumes the parameters, so the next step's frozen-ViT / early-layer GEMMs (MFMA-bound) overlap it
-        self.opt_stream = mk(priority=int(os.environ.get('VLASER_SFT_OPT_PRIORITY', '0')))
+        self.opt_stream = mk()
         # r04: the layer weight gradients run on a stream of their own.  dW = dY^T X depends on dY only, nothing in the backward chain depends on it, and most
         # of the chain's launches are single-round grids of 108-252 workgroups on 256 CUs (tools/micro/sft_timeline.py): the weight-gradient GEMMs fill the gaps
-        self._slab_norm = os.environ.get('VLASER_SFT_NO_SLAB_NORM') != '1'      # A/B: reduce the gate/up dgrad's slabs in their own launch again
-        self.wgrad_stream = None if os.environ.get('VLASER_SFT_NO_WGRAD_STREAM') == '1' else mk()
+        self.wgrad_stream = mk()
 
     def exchange_info(self):
         """What the step's exchange runs on (bench.py puts it on the line as `sft.exchange.mode` ...)."""
@@ -373,7 +369,7 @@ class SFTModel(ParamGroup):
         rows whose dY pad rows are zero (`_zero_wgrad_pad`): the product then runs on the LDS-DMA pipeline (r03: 97 instead of 135 us
         per layer at S = 560, tools/micro/tn_lab.py)."""
         Sp = (S + 63) // 64 * 64
-        if padded and self.wgrad_lds and dY.shape[1] % 8 == 0 and X.shape[1] % 8 == 0:
+        if padded and dY.shape[1] % 8 == 0 and X.shape[1] % 8 == 0:
             for t in (dY, X):       # the pad rows must lie inside the buffer the view was cut from
                 if t.storage_offset() + (Sp - 1) * t.stride(0) + t.shape[1] > t.untyped_storage().nbytes() // t.element_size():
                     raise ValueError(f'_wgrad(padded=True): the operand has no {Sp - S} pad rows behind its {S} rows')
@@ -437,9 +433,6 @@ class SFTModel(ParamGroup):
     def _wgrad_side(self, *args, want_done=False, **kw):
         """`_wgrad` on the weight-gradient stream, behind everything the compute stream has queued so far (its dY operand); `want_done`: returns the event
         that marks its end."""
-        if self.wgrad_stream is None:
-            self._wgrad(*args, **kw)
-            return None
         ev = torch.cuda.Event()
         ev.record()
         ws = self.wgrad_stream
@@ -459,8 +452,7 @@ class SFTModel(ParamGroup):
 
     def _join_wgrad(self):
         """The compute stream waits for every weight gradient queued so far (before their dY buffers are overwritten / the bucket is handed on)."""
-        if self.wgrad_stream is not None:
-            torch.cuda.current_stream().wait_stream(self.wgrad_stream)
+        torch.cuda.current_stream().wait_stream(self.wgrad_stream)
 
     def _zero_wgrad_pad(self, S):
         """Rows S..ceil64(S) of the four dY buffers the layer weight gradients contract over: zero, so that the padded TN GEMM may read whole
@@ -620,8 +612,7 @@ class SFTModel(ParamGroup):
         ops.embed_merge(ids, v['embed'], feat_used, h0, self.img_context_token_id, cfg.pad_token_id, False, self.rank_ws)
         # ---- forward through the layers (saved activations per layer, or only the layer inputs when recompute=True)
         # r04: the down_proj seam (split-K reduce + residual) also applies the following layer's input_layernorm into its x1 slot, as the inference prefill
-        # does: one launch less per layer (`VLASER_SFT_NO_SEAM_NORM=1`: A/B)
-        seam = os.environ.get('VLASER_SFT_NO_SEAM_NORM') != '1'
+        # does: one launch less per layer
         xn = self.xn[:S]
         bucket_of = self.bucket_of_layer
         x1_ready = False
@@ -629,7 +620,7 @@ class SFTModel(ParamGroup):
             self._wait_params(bucket_of[i])
             _, _, h2, _, _, _, act = self._layer_forward(i, self.h_in[i, :S], S, pos, x1_ready=x1_ready)
             # (only inside a parameter bucket: across a boundary the seam would have to wait for the NEXT bucket's AdamW / all-gather one GEMM early)
-            x1_ready = seam and i + 1 < Lyr and bucket_of[i + 1] == bucket_of[i]
+            x1_ready = i + 1 < Lyr and bucket_of[i + 1] == bucket_of[i]
             if x1_ready:
                 self._layer_out(i, S, h2, act, self.h_in[i + 1, :S], norm_w=v[f'l{i + 1}.ln_in'], x_out=self._saved(i + 1, S)[0])
             else:
@@ -669,7 +660,7 @@ class SFTModel(ParamGroup):
         dx_rows = torch.empty(R, H, dtype=BF, device=dev)
         # dX = dlogits @ W_head (contraction over Vp: dlogits and the pad rows are zero there): R rows against a 466 MB weight is a stream, and the stream
         # wants many slices in flight -- 30 split-K slices 114 us (4.1 TB/s), the generic chooser's 6 slices 210 us (tools/micro/head_lab.py)
-        sp = max(d for d in range(1, int(os.environ.get('VLASER_SFT_HEAD_SPLITS', '32')) + 1) if self.Vp % (64 * d) == 0)
+        sp = max(d for d in range(1, 33) if self.Vp % (64 * d) == 0)
         if sp > 8 and sp * R * H <= self.part.numel():
             part = self.part[:sp * R * H]
             ops.gemm_nn(L.EPI_PARTIAL, dlog, self.head_full, out_f32=part, k_splits=sp)
@@ -689,6 +680,8 @@ class SFTModel(ParamGroup):
         sm = self.cache.s_max
         scale = hd ** -0.5
         nslot = 0                       # norm-weight gradients of the current bucket whose partials wait in self.normw_multi
+        nw = self.normw_multi
+        slot = lambda k: nw[k * self.normw_slot:(k + 1) * self.normw_slot]
         for i in reversed(range(Lyr)):
             h_in = self.h_in[i, :S]
             self._join_wgrad()          # the previous layer's weight gradients still read dgu / dh2 / dqkv (and, with recompute, the one activation slot)
@@ -696,7 +689,7 @@ class SFTModel(ParamGroup):
             kslot = 0 if self.recompute else i
             dact, dgu, dx, dh2, dao = self.dact[:S], self.dgu[:S], self.dx[:S], self.dh2[:S], self.dao[:S]
             # MLP: h3 = h2 + act Wd^T ; act = silu(g) u ; [g|u] = x2 Wgu^T ; x2 = rms(h2) w_post
-            if H <= 2048 and os.environ.get('VLASER_SFT_NO_FUSED_SWIGLU_BWD') != '1':
+            if H <= 2048:
                 # d(act) = dh @ W_down with swiglu's backward as the GEMM epilogue: d(gate), d(up) straight from the accumulators
                 # (the stand-alone pass read d(act) and the pre-activations back and wrote 2 I columns per row)
                 ops.gemm_nn(L.EPI_SWIGLU_BWD, dh, v[f'l{i}.wdown'], out=dgu, res=gu)
@@ -704,15 +697,13 @@ class SFTModel(ParamGroup):
                 backward.dgrad_nn(dh, v[f'l{i}.wdown'], dact, self.part)
                 ops.swiglu_bwd(gu, dact, dgu, S, I)
             ev_wdown = self._wgrad_side(dh, act, gv[f'l{i}.wdown'], S, padded=True, ssq=self._ssq(f'l{i}.wdown'), want_done=True)
-            slabs = backward.dgrad_nn(dgu, v[f'l{i}.wgu'], dx, self.part, keep_slabs=self._slab_norm)
+            slabs = backward.dgrad_nn(dgu, v[f'l{i}.wgu'], dx, self.part, keep_slabs=True)
             self._wgrad_side(dgu, x2, gv[f'l{i}.wgu'], S, padded=True, ssq=self._ssq(f'l{i}.wgu'))
-            nw = self.normw_multi
-            dw_kw = dict(dw_out=gv[f'l{i}.ln_post'], dw_ws=self.normw_ws) if nw is None else dict(dw_ws=nw[nslot * self.normw_slot:(nslot + 1) * self.normw_slot])
             if slabs is not None:       # r04: the split-K slabs of the gate/up dgrad go straight into the norm's backward (one launch less per layer, same bits)
-                ops.rmsnorm_bwd(None, h2, v[f'l{i}.ln_post'], dh, dh2, S, H, llm.rms_norm_eps, dy_partials=slabs[0], n_partials=slabs[1], **dw_kw)
+                ops.rmsnorm_bwd(None, h2, v[f'l{i}.ln_post'], dh, dh2, S, H, llm.rms_norm_eps, dy_partials=slabs[0], n_partials=slabs[1], dw_ws=slot(nslot))
             else:
-                ops.rmsnorm_bwd(dx, h2, v[f'l{i}.ln_post'], dh, dh2, S, H, llm.rms_norm_eps, **dw_kw)
-            nslot += nw is not None
+                ops.rmsnorm_bwd(dx, h2, v[f'l{i}.ln_post'], dh, dh2, S, H, llm.rms_norm_eps, dw_ws=slot(nslot))
+            nslot += 1
             # attention block: h2 = h_in + ao Wo^T
             backward.dgrad_nn(dh2, v[f'l{i}.wo'], dao, self.part)
             self._wgrad_side(dh2, ao, gv[f'l{i}.wo'], S, padded=True, ssq=self._ssq(f'l{i}.wo'))
@@ -728,13 +719,11 @@ class SFTModel(ParamGroup):
             ops.rope_bwd_pack(self.dq[:S], self.dk[:S], self.dv[:S], self.rope[0], self.rope[1], pos, dqkv, S, nq, nkv, kv_per_q_head=True)
             backward.dgrad_nn(dqkv, v[f'l{i}.wqkv'], dx, self.part)
             self._wgrad_side(dqkv, x1, gv[f'l{i}.wqkv'], S, bias_out=gv[f'l{i}.bqkv'], padded=True, ssq=self._ssq(f'l{i}.wqkv'))
-            if ev_wdown is not None:
-                torch.cuda.current_stream().wait_event(ev_wdown)          # the down_proj weight gradient read dh, which the next kernel overwrites
-            dw_kw = dict(dw_out=gv[f'l{i}.ln_in'], dw_ws=self.normw_ws) if nw is None else dict(dw_ws=nw[nslot * self.normw_slot:(nslot + 1) * self.normw_slot])
-            ops.rmsnorm_bwd(dx, h_in, v[f'l{i}.ln_in'], dh2, dh, S, H, llm.rms_norm_eps, **dw_kw)
-            nslot += nw is not None
+            torch.cuda.current_stream().wait_event(ev_wdown)          # the down_proj weight gradient read dh, which the next kernel overwrites
+            ops.rmsnorm_bwd(dx, h_in, v[f'l{i}.ln_in'], dh2, dh, S, H, llm.rms_norm_eps, dw_ws=slot(nslot))
+            nslot += 1
             last_of_bucket = i == 0 or bucket_of[i - 1] != bucket_of[i]
-            if nw is not None and last_of_bucket:
+            if last_of_bucket:
                 # the bucket's layers are i .. i + nslot/2 - 1, visited last to first: slots = (ln_post, ln_in) of layer i + nslot/2 - 1, ..., of layer i
                 key = (i, nslot)
                 if key not in self._normw_off:
@@ -849,7 +838,7 @@ class SFTModel(ParamGroup):
         def adamw(b):
             self.adamw_bucket(b, lr, self.betas, self.eps, self.wd, self.gnorm2, self.max_grad_norm, self.step_count)
 
-        if not self.dp_active and self.overlap_optimizer:
+        if not self.dp_active:
             # pipelined with the NEXT step: bucket by bucket on `opt_stream`, embed + projector first, lm_head last; the next forward
             # waits per bucket (`_wait_params`); by the time its backward starts every bucket has been waited for.  The
             # update is therefore still in flight when this returns: `wait_optimizer()` before touching parameter buffers directly.
@@ -858,7 +847,7 @@ class SFTModel(ParamGroup):
                     adamw(b)
                     self._mark_params(b)
             return gnorm
-        if self.dp_active and self.overlap_allgather and os.environ.get('VLASER_SFT_DP_SERIAL_ADAMW') != '1':
+        if os.environ.get('VLASER_SFT_DP_SERIAL_ADAMW') != '1':
             # ZeRO-1 (r03): this rank's shard of every bucket is updated ON THE COMM STREAM right in front of that bucket's parameter all-gather, bucket by
             # bucket in the order the NEXT forward consumes them (embed + projector first, lm_head last); the forward waits per bucket (`_wait_params`), so
             # AdamW (1/N of the parameters) and the exchange both run under the frozen ViT and the earlier layers instead of between two steps
@@ -877,15 +866,13 @@ class SFTModel(ParamGroup):
                     adamw(b)
                     self._gather_bucket(b)
             return gnorm
+        # VLASER_SFT_DP_SERIAL_ADAMW=1: every bucket's AdamW on the compute stream first, then the all-gathers of the updated bf16 parameters bucket by
+        # bucket on the comm stream, in the order the NEXT forward consumes them
         for b in range(len(self.buckets)):
             adamw(b)
-        if self.dp_active:
-            # all-gather the updated bf16 parameters bucket by bucket on the comm stream, in the order the NEXT forward consumes them
-            with behind_current(self.comm_stream):
-                for b in reversed(range(len(self.buckets))):
-                    self._gather_bucket(b)
-            if not self.overlap_allgather:
-                torch.cuda.current_stream().wait_stream(self.comm_stream)
+        with behind_current(self.comm_stream):
+            for b in reversed(range(len(self.buckets))):
+                self._gather_bucket(b)
         return gnorm
 
     def step(self, pixel_values, input_ids, labels, image_flags=None, lr=None, total_steps=None):
@@ -975,14 +962,13 @@ class SFTModel(ParamGroup):
             if len(wk) > 5:
                 self._grow_rows(int(wk[5].ids.numel()))
         if len(work) == 1 and work[0][4] == 1.0:
-            early = not self.dp_active and self.overlap_optimizer and os.environ.get('VLASER_SFT_NO_EARLY_NORM') != '1'
+            early = not self.dp_active
             self._norm_buckets_seen = 0
             # the norm from the producers (r04) needs every gradient element to be written exactly once by a kernel that can sum it: one sample per step
             # (or one batch-rows pass: the weight gradients then contract over the M concatenated rows in ONE launch each -- vlaser_gemm_tn_lds never splits its
             # contraction, and its tile choice, hence the slots it reaches, follows the weight's shape and the CU budget, not the row count)
-            # ... and a slot layout that depends on the weight's shape only: true for the LDS-DMA weight-gradient kernel the step takes by default; the A/B fallback
-            # (VLASER_SFT_WGRAD=tn) picks its kernel -- and with it the slots it reaches -- by the sequence length, so it keeps the buffer pass
-            self._fused_norm = early and self.wgrad_lds and os.environ.get('VLASER_SFT_NO_FUSED_NORM') != '1'
+            # ... and a slot layout that depends on the weight's shape only: true for the LDS-DMA weight-gradient kernel the step takes
+            self._fused_norm = early and os.environ.get('VLASER_SFT_NO_FUSED_NORM') != '1'
             if self._fused_norm and self.norm_parts is None:
                 self._plan_fused_norm()
             try:

@@ -17,13 +17,12 @@ Forward = the inference kernels with every intermediate kept (the image/text row
 (NN dgrad on the weights as stored, TN wgrad, RMSNorm / SwiGLU / RoPE backward) with a bidirectional mask, plus LayerNorm / GELU / layer-scale /
 full-attention backward for the vision tower.  All arithmetic is HIP through the C ABI; torch holds buffers and does index plumbing.
 """
-import os
 
 import torch
 
 from . import _lib as L
 from . import ops
-from .backward import attn_bwd_materialised, dgrad_nn, projector_backward, projector_forward, wgrad_tn
+from .backward import dgrad_nn, projector_backward, projector_forward, wgrad_tn
 from .engine import BF
 from .param_group import DECODER_LAYER_NAMES, MLP1_KEYS, FlatParams, ParamGroup, decoder_layer_specs, mlp1_specs, unpack_decoder_layer, unpack_mlp1
 
@@ -98,7 +97,6 @@ class VLMGroup(ParamGroup):
         self.gu, self.act = z(Lyr, T, 2 * I), z(Lyr, T, I)
         self.part = torch.zeros(ops.split_slab_elems(max(T, vis.num_positions), max(H, vis.hidden_size)), dtype=F32, device=dev)
         # ---- backward buffers (LLM rows)
-        self.Tp = (T + 63) // 64 * 64
         self.dh, self.dh2, self.dx = z(T, H), z(T, H), z(T, H)
         self.dgu = z(T, 2 * I)
         self.dao, self.dq, self.dk, self.dv = z(T, nq * hd), z(T, nq * hd), z(T, nq * hd), z(T, nq * hd)
@@ -109,7 +107,6 @@ class VLMGroup(ParamGroup):
         # fused attention backward of the VLM rows (r06): the forward's base-2 log-sum-exp per layer + the kernel's delta scratch
         self.lse = torch.zeros(llm.num_hidden_layers, nq * T, dtype=F32, device=dev)
         self.delta_ws = torch.zeros(nq * T, dtype=F32, device=dev)
-        self.fused_attn_bwd = os.environ.get('VLASER_VLA_VLM_ATTN_BWD', 'fused') != 'materialised'
         # ---- vision tower: saved activations per block + projector intermediates
         S, C, Cm, Hn, hdv = vis.num_positions, vis.hidden_size, vis.intermediate_size, vis.num_attention_heads, vis.head_dim
         sp = self.sp = tr.vit.s_pad
@@ -121,8 +118,8 @@ class VLMGroup(ParamGroup):
         C4 = 4 * C
         self.ps_raw, self.ps_ln = z(nt, C4), z(nt, C4)
         self.z1, self.g1, self.feat = z(nt, H), z(nt, H), z(nt, H)
-        # ---- backward buffers (vision / projector); the score matrices are shared by both towers' attention backward
-        n_sc = max(nq * T * self.Tp, Hn * S * sp)
+        # ---- backward buffers (vision / projector); the score matrices of the vision tower's attention backward
+        n_sc = Hn * S * sp
         self.sc = torch.zeros(n_sc, dtype=F32, device=dev)
         self.dP = torch.zeros(n_sc, dtype=F32, device=dev)
         self.P, self.dS = z(n_sc), z(n_sc)
@@ -218,10 +215,10 @@ class VLMGroup(ParamGroup):
         gradients of this layer's joint attention; leaves d loss / d h_in[i] in self.dh."""
         tr, llm = self.tr, self.llm
         v, gv = self.fp.view, self.fp.gview
-        T, Tp = tr.T, self.Tp
+        T = tr.T
         H, I = llm.hidden_size, llm.intermediate_size
         nq, nkv, hd = llm.num_attention_heads, llm.num_key_value_heads, llm.head_dim
-        G, sm, scale = nq // nkv, tr.s_max, hd ** -0.5
+        sm, scale = tr.s_max, hd ** -0.5
         Lyr = llm.num_hidden_layers
         g = lambda nm: v[f'l{i}.{nm}']
         gg = lambda nm: gv[f'l{i}.{nm}']
@@ -236,16 +233,10 @@ class VLMGroup(ParamGroup):
             wgrad_tn(dh2, self.ao[i], gg('wo'))
             # attention backward; key k visible iff k < n_valid (bidirectional inside the valid prefix)
             Kc, VTc = tr.cache.k[i, 0], tr.cache.vt[i, 0]
-            if self.fused_attn_bwd:
-                # r06: the SFT step's fused kernel (csrc/attn_bwd.hip; causal = 0, kv_valid = the prefix length) instead of six launches through materialised
-                # [heads, T, T] fp32 score matrices: ~200 -> ~40 us per layer (profiles/r06ab_vla_train_kernel_stats.md)
-                ops.attn_bwd(self.q[i], Kc, VTc, self.ao[i], dao, self.lse[i], self.delta_ws, self.dq, self.dk, self.dv, T, nq, nkv, sm, scale, causal=False,
-                             kv_valid=n_valid, head_dim=hd)
-            else:
-                n = nq * T * Tp
-                sc, dP = self.sc[:n].view(nq, T, Tp), self.dP[:n].view(nq, T, Tp)
-                P, dS = self.P[:n].view(nq, T, Tp), self.dS[:n].view(nq, T, Tp)
-                attn_bwd_materialised(self.q[i], Kc, VTc, dao, self.ao[i], sc, dP, P, dS, self.dq, self.dk, self.dv, T, T, Tp, nq, G, hd, sm, scale, False, n_valid)
+            # r06: the SFT step's fused kernel (csrc/attn_bwd.hip; causal = 0, kv_valid = the prefix length) instead of six launches through materialised
+            # [heads, T, T] fp32 score matrices: ~200 -> ~40 us per layer (profiles/r06ab_vla_train_kernel_stats.md)
+            ops.attn_bwd(self.q[i], Kc, VTc, self.ao[i], dao, self.lse[i], self.delta_ws, self.dq, self.dk, self.dv, T, nq, nkv, sm, scale, causal=False,
+                         kv_valid=n_valid, head_dim=hd)
             ops.rope_bwd_pack_ex(self.dq, self.dk, self.dv, tr.rope[0], tr.rope[1], tr.pos_vlm, dqkv, T, nq, nkv, kv_per_q_head=True, dk_extra=self.dkx,
                                  dv_extra=self.dvx)
             dres = dh2
