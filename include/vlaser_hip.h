@@ -204,7 +204,7 @@ int vlaser_skinny(int prologue, int epi, const VlaserSkinnyArgs* args, vl_stream
  *   vlaser_chain_down: h_out [M, N] = bf16(res + x [M, K] @ W^T), W = down_proj.weight packed by ops.pack_down4 ([workgroup][7 waves][10 loads][groups][16 blocks][cols][8]):
  *                      a workgroup owns `groups` x `cols` output columns (vlaser_chain_down_geometry) over the whole K = 8960 (no cross-workgroup split-K); res != h_out
  * *_supported(...) != 0 tells the host surface whether a geometry has a variant (it keeps vlaser_skinny otherwise). */
-/*   vlaser_chain_attn : vlaser_attn_skinny's arguments; one WAVE per (kv head, key split, batch element) with 2 chunks of 32 keys each (no LDS merge, no barrier);
+/*   vlaser_chain_attn : vlaser_attn_skinny's arguments; one WAVE per (kv head, key split, 16-row tile, batch element) with 2 chunks of 32 keys each (no LDS merge, no barrier);
  *                       part_m = fp32 [B, n_kv, n_splits, 32, 2] (m, l) pairs, part_o = BF16 [B, n_kv, n_splits, 32, 128] NORMALISED rows (part_l unused);
  *                       n_splits = vlaser_chain_attn_splits(kv_len) = ceil(ceil(kv_len / 32) / 2) <= 16
  *   vlaser_chain_oproj: args as vlaser_skinny(VL_PRO_ATTN, VL_SK_PARTIAL) with tiles_per_unit = 1, attn_m / attn_o = what vlaser_chain_attn wrote: merge of the splits

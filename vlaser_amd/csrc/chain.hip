@@ -646,8 +646,8 @@ extern "C" int vlaser_chain_down2(const void* x, int ldx, const void* W, float* 
 }
 
 // ------------------------------------------------------------------------------------------------------------------ attention over the KV cache, <= 16 query tokens
-// One WAVE per (kv head, key split, batch element), NC 32-key chunks each, no LDS, no barrier: Q of the kv head's (q head, token) rows (<= 32 rows = two MFMA
-// tiles), then K and V^T of every chunk of the wave are requested in one burst (vlaser_attn_skinny staged the same work through 4-wave workgroups whose merge
+// One WAVE per (kv head, key split, 16-row tile, batch element), NC 32-key chunks each, no LDS, no barrier: Q of the tile's (q head, token) rows (the kv head has
+// <= 32 rows = two MFMA tiles), then K and V^T of every chunk of the wave are requested in one burst (vlaser_attn_skinny staged the same work through 4-wave workgroups whose merge
 // through LDS was 1.0 us of its 6.1 us, and its vector load of valid_len[b] put an `s_waitcnt vmcnt(0)` -- a second full round trip -- between the Q and the K / V^T
 // requests).  A split leaves (m, l) fp32 and its NORMALISED output rows in bf16 (half the bytes of the fp32 partials for the 144 workgroups of the o_proj launch
 // that each merge the splits of their K range); chain_oproj weights them by l 2^(m - max m).
@@ -657,17 +657,21 @@ struct ChainAttnP {
   const int32_t* valid_len;
   long long q_bs, q_hs, q_ss, k_bs, k_hs, vt_bs, vt_hs;
   int sq, kv_len, G, ld_vt, mode, blk_start, first_tok_kv_len, n_splits, n_kv;
+  int tile_sh;                                        // 1: grid.y = 2 split + row tile (one wave per 16-row tile), 0: grid.y = split
   float scale;
   unsigned long long* dbg;
   const float* mask; long long mask_bs, mask_rs;      // VL_ATTN_DENSE (ABI 8): fp32 additive mask, row = query TOKEN (the same for every head)
 };
 
 // DENSE: the visibility and a bias per (token, key) come from p.mask instead of the (valid_len, blk_start) descriptors; requested with the K / V^T of the chunks
-template <int NC, bool DBG, bool DENSE = false>
+// QT: the 16-row tiles a wave walks.  No row reads another row's result, so with more than 16 rows the launch gives every tile a wave of its own (QT = 1, grid.y =
+// 2 splits + tile: the two waves of a split are neighbours and request the same K / V^T) instead of running the second tile's chain behind the first's; with
+// <= 16 rows (a greedy decode step) the second tile has no row and is not computed.
+template <int NC, int QT, bool DBG, bool DENSE = false>
 __global__ __launch_bounds__(64) void chain_attn_kernel(ChainAttnP p) {
   constexpr int HD = 128, DC = 4, DT = 8;
   const int lane = threadIdx.x, fr = lane & 15, g = lane >> 4;
-  const int kvh = blockIdx.x, split = blockIdx.y, b = blockIdx.z;
+  const int kvh = blockIdx.x, split = blockIdx.y >> p.tile_sh, tile0 = blockIdx.y & p.tile_sh, b = blockIdx.z;
   unsigned long long* dbg = DBG ? p.dbg + (((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8 : nullptr;
   CH_STAMP(0);
   const int nq = p.sq, nrows = p.G * nq;
@@ -675,11 +679,11 @@ __global__ __launch_bounds__(64) void chain_attn_kernel(ChainAttnP p) {
   const bf16_t* VT = p.vt + (size_t)b * p.vt_bs + (size_t)kvh * p.vt_hs;
   const int n_chunks = (p.kv_len + 31) >> 5;
   // ---- every request of the wave: Q rows (written by the previous launch), then K / V^T of its NC chunks (clamped: a chunk past the end is fully masked)
-  u32x4 qv[2][DC];
-  int row_hi2[2];
+  u32x4 qv[QT][DC];
+  int row_hi2[QT];
 #pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const int r = min(qt * 16 + fr, nrows - 1);
+  for (int qt = 0; qt < QT; ++qt) {
+    const int r = min((tile0 + qt) * 16 + fr, nrows - 1);
     const int hg = (int)(((float)r + 0.5f) * __builtin_amdgcn_rcpf((float)nq)), tok = r - hg * nq;
     row_hi2[qt] = (tok == 0 && p.first_tok_kv_len > 0) ? p.first_tok_kv_len : 0x7fffffff;
     const bf16_t* Q = p.q + (size_t)b * p.q_bs + (size_t)(kvh * p.G + hg) * p.q_hs + (size_t)tok * p.q_ss;
@@ -699,11 +703,11 @@ __global__ __launch_bounds__(64) void chain_attn_kernel(ChainAttnP p) {
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) vf[c][dt] = ld_global_16(VT + (size_t)(dt * 16 + fr) * p.ld_vt + key0 + g * 8);
   }
-  f32x4 mk[DENSE ? 2 : 1][DENSE ? NC : 1][2];
+  f32x4 mk[DENSE ? QT : 1][DENSE ? NC : 1][2];
   if constexpr (DENSE) {
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-      const int r = min(qt * 16 + fr, nrows - 1);
+    for (int qt = 0; qt < QT; ++qt) {
+      const int r = min((tile0 + qt) * 16 + fr, nrows - 1);
       const int hg = (int)(((float)r + 0.5f) * __builtin_amdgcn_rcpf((float)nq)), tok = r - hg * nq;
       const float* mrow = p.mask + (size_t)b * p.mask_bs + (size_t)tok * p.mask_rs;
 #pragma unroll
@@ -721,12 +725,14 @@ __global__ __launch_bounds__(64) void chain_attn_kernel(ChainAttnP p) {
     lim1 = min(p.valid_len ? vl_sload_i32(p.valid_len + b) : p.kv_len, p.kv_len);      // scalar cache: not in the vmcnt queue
     lo2 = p.blk_start; hi2 = p.kv_len;
   }
-  f32x4 o[2][DT];
+  f32x4 o[QT][DT];
 #pragma unroll
-  for (int qt = 0; qt < 2; ++qt)
+  for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
     for (int i = 0; i < DT; ++i) o[qt][i] = f32x4{0, 0, 0, 0};
-  float m_run[2] = {-1.0e30f, -1.0e30f}, l_run[2] = {0.f, 0.f};
+  float m_run[QT], l_run[QT];
+#pragma unroll
+  for (int qt = 0; qt < QT; ++qt) { m_run[qt] = -1.0e30f; l_run[qt] = 0.f; }
   const float sc = p.scale * 1.4426950408889634f;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
@@ -742,7 +748,7 @@ __global__ __launch_bounds__(64) void chain_attn_kernel(ChainAttnP p) {
         visk[t][r] = live & ((key < lim1) | ((key >= lo2) & (key < hi2)));        // bitwise: `&&` / `||` on lane-varying flags become exec-branch blocks
       }
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
+    for (int qt = 0; qt < QT; ++qt) {
       f32x4 s[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -792,12 +798,12 @@ __global__ __launch_bounds__(64) void chain_attn_kernel(ChainAttnP p) {
   }
   if constexpr (DBG) asm volatile("" ::"v"(o[0][0][0]));
   CH_STAMP(1);
-  // ---- the split's partial: (m, l) and the normalised rows (bf16); lane (fr, g) holds d = 16 dt + 4 g .. + 4 of row 16 qt + fr
+  // ---- the split's partial: (m, l) and the normalised rows (bf16); lane (fr, g) holds d = 16 dt + 4 g .. + 4 of row 16 (tile0 + qt) + fr
   const size_t pidx = ((size_t)b * p.n_kv + kvh) * p.n_splits + split;
 #pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
+  for (int qt = 0; qt < QT; ++qt) {
     const float l_tot = vl_xor32_sum(vl_xor16_sum(l_run[qt]));
-    const int row = qt * 16 + fr;
+    const int row = (tile0 + qt) * 16 + fr;
     if (row < nrows) {
       if (g == 0) *reinterpret_cast<f32x2_t*>(p.pml + (pidx * 32 + row) * 2) = f32x2_t{m_run[qt], l_tot};
       const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
@@ -826,10 +832,11 @@ extern "C" int vlaser_chain_attn(const VlaserAttnArgs* a, vl_stream_t s) {
   p.sq = a->sq; p.kv_len = a->kv_len; p.G = a->n_q_heads / a->n_kv_heads; p.ld_vt = a->ld_vt; p.mode = a->mode; p.blk_start = a->blk_start;
   p.first_tok_kv_len = a->first_tok_kv_len; p.n_splits = a->n_splits; p.n_kv = a->n_kv_heads; p.scale = a->scale; p.dbg = a->dbg;
   p.mask = a->mask; p.mask_bs = a->mask_bs; p.mask_rs = a->mask_rs;
-  const dim3 grid(a->n_kv_heads, a->n_splits, a->batch);
-  if (a->mode == VL_ATTN_DENSE) hipLaunchKernelGGL((chain_attn_kernel<2, false, true>), grid, dim3(64), 0, (hipStream_t)s, p);
-  else if (p.dbg) hipLaunchKernelGGL((chain_attn_kernel<2, true>), grid, dim3(64), 0, (hipStream_t)s, p);
-  else hipLaunchKernelGGL((chain_attn_kernel<2, false>), grid, dim3(64), 0, (hipStream_t)s, p);
+  p.tile_sh = a->sq * p.G > 16 ? 1 : 0;
+  const dim3 grid(a->n_kv_heads, a->n_splits << p.tile_sh, a->batch);
+  if (a->mode == VL_ATTN_DENSE) hipLaunchKernelGGL((chain_attn_kernel<2, 1, false, true>), grid, dim3(64), 0, (hipStream_t)s, p);
+  else if (p.dbg) hipLaunchKernelGGL((chain_attn_kernel<2, 1, true>), grid, dim3(64), 0, (hipStream_t)s, p);
+  else hipLaunchKernelGGL((chain_attn_kernel<2, 1, false>), grid, dim3(64), 0, (hipStream_t)s, p);
   VL_LAUNCH_CHECK();
   return 0;
 }
