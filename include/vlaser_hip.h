@@ -61,8 +61,45 @@ typedef struct {
   void* vq; void* vk; void* vvt; int vit_heads, vit_seq, vit_seq_pad; float q_scale;
   /* VL_EPI_PARTIAL */
   float* out_f32; int k_splits;
-  int force_bm;             /* 0 = heuristic; 32 / 64 / 128 = register-staged tile height; 1100 / 1200 / 1300 / 1440 / 1500 = LDS-DMA pipeline
-                               128x128 / 128x256 / 256x256 / 144x128 / 64x128 (tests, tools/micro/gemm_lab) */
+  int force_bm;             /* 0 = heuristic, or a configuration code (tests, tools/micro).  THE table of codes; a code outside it, or outside its form, is refused
+   * before any launch.  NT = vlaser_gemm, NN = vlaser_gemm_nn, TN = vlaser_gemm_tn_lds (its force_cfg).  tile = rows x columns of a workgroup; waves; st = stages of the
+   * LDS ring (K-tiles of 64); flags as in csrc/gemm.hip: I = IFIRST (refill requested in front of the fragment reads), A = ASYM (W ring one stage deeper), S = SPREAD
+   * (refill pieces between the MFMAs), P = PIPE (fragment reads pipelined across the barrier), - = plain loop, refill as one burst.  default = the heuristic picks it.
+   *   code   tile      waves  st  flags  forms       use
+   *   32/64/128  (32|64|128)x128  4  -  -      NT          register-staged kernel; default 32 for M <= 32
+   *   1100   128x128   8      4   S      NT NN       default
+   *   1100   128x128   8      4   -      TN          default
+   *   1101   128x128   8      4   -      NT NN       lab: 1100 before SPREAD
+   *   1110   128x128   8      4   S P    NT NN       lab: PIPE on 128x128 (noise)
+   *   1110   128x128   8      4   P      TN          lab
+   *   1105   128x128   8      5   -      NT NN TN    lab: deeper ring
+   *   1200   128x256   8      3   S      NT NN       default
+   *   1200   128x256   8      3   -      TN          default
+   *   1201   128x256   8      3   -      NT NN       lab: 1200 before SPREAD
+   *   1210   128x256   8      3   S P    NT NN       lab: PIPE on 128x256 (noise)
+   *   1210   128x256   8      3   P      TN          lab
+   *   1300   256x256   8      2   A S    NT NN       default
+   *   1300   256x256   8      2   -      TN          default
+   *   1301   256x256   8      2   I      NT NN       lab
+   *   1302   256x256   8      2   -      NT NN       lab: the two-stage ring before ASYM
+   *   1304   256x256   8      2   A      NT NN       lab: ASYM, burst refill
+   *   1310   256x256   8      2   A S P  NT          lab: PIPE on 256x256 (the NN form's transposing reads would spill)
+   *   1440   144x128   6      4   S P    NT NN       default (M = 8 x 128 + a few rows)
+   *   1441   144x128   6      4   -      NT NN       lab
+   *   1442   144x128   6      4   S      NT NN       lab: 1440 before PIPE
+   *   1500   64x128    8      4   S P    NT NN       default
+   *   1501   64x128    8      4   -      NT NN       lab
+   *   1502   64x128    8      4   S      NT NN       lab: 1500 before PIPE
+   *   1506   64x128    8      6   -      NT NN       lab: deeper ring
+   *   1532   32x128    4      7   -      NT NN       lab
+   *   1564   64x64     4      8   P      NT          default (smallest problems)
+   *   1566   64x64     4      8   -      NT          lab: 1564 before PIPE
+   *   1900   192x256   8      2   A S P  NT NN       default (rows = 3 x 192: the SFT step's 560)
+   *   1901   192x256   8      2   I      NT NN       lab
+   *   1902   192x256   8      2   A S    NT NN       lab: 1900 before PIPE
+   *   1903   192x256   8      2   I A    NT NN       lab
+   *   1904   192x256   8      2   A      NT NN       lab: ASYM, burst refill
+   *   1140 / 1240 / 1340  128x128 / 128x256 / 256x256  8  4 x 32 k  -  TN, plain bf16 output only   two staggered wave groups; 1340 default for multi-round grids */
   /* batched GEMM (attention backward through materialised per-head matrices): blockIdx.z = batch index z;
    * A += z*a_bs, out += z*o_bs, W += (z / w_group)*w_bs  (element strides; batch 0/1 = plain GEMM) */
   int batch; long long a_bs, w_bs, o_bs; int w_group;
@@ -95,7 +132,7 @@ int vlaser_stream_destroy(vl_stream_t stream);
  * (dX = dY @ W, autograd of modeling_internvl_chat.py:194-203 / joint_model.py:410-696) reads the forward weight [N_out, K_in] as it
  * is stored: no transposed copy.  Epilogues VL_EPI_NONE (bf16 out), VL_EPI_F32, VL_EPI_PARTIAL (split-K fp32 slabs) and VL_EPI_SWIGLU_BWD; batched like
  * vlaser_gemm for NONE / F32 (the attention backward's dP = dO V^T and dQ = dS K read V^T / K as the cache holds them); K % 64 == 0, N % 8 == 0;
- * force_bm: 0 or an LDS-DMA configuration code. */
+ * force_bm: 0 or a code of the NN column of the table at VlaserGemmArgs.force_bm. */
 int vlaser_gemm_nn(int epi, const VlaserGemmArgs* args, vl_stream_t stream);
 
 /* ---- attention ------------------------------------------------------------------------------------------------
@@ -266,7 +303,7 @@ int vlaser_gemm_tn(const void* At, const void* Wt, void* out, int M, int N, int 
                    vl_stream_t stream);
 /* The same TN product on the LDS-DMA GEMM pipeline (8 waves, 128x128 .. 256x256 tiles, both operands global -> LDS without staging registers,
  * fragments through the transposing LDS read).  Contract: K is a whole number of 64-row tiles; rows K_true..K of At are ZERO and those of Wt finite
- * (the SFT step pads its sequence axis: sft.py `_wgrad`); ldat, ldwt multiples of 8 and >= M / N rounded up to 8 (rows are read in 16-byte pieces).  force_cfg: 0 = heuristic, or 1100 / 1105 / 1200 / 1300.
+ * (the SFT step pads its sequence axis: sft.py `_wgrad`); ldat, ldwt multiples of 8 and >= M / N rounded up to 8 (rows are read in 16-byte pieces).  force_cfg: 0 = heuristic, or a code of the TN column of the table at VlaserGemmArgs.force_bm.
  * sumsq_part / sumsq_cap: as for vlaser_gemm_tn; sumsq_cap >= ceil(M/128) * ceil(N/128) * 8 always suffices. */
 int vlaser_gemm_tn_lds(const void* At, const void* Wt, void* out, int M, int N, int K, int ldat, int ldwt, int ldo, int force_cfg, float* sumsq_part,
                        int sumsq_cap, vl_stream_t stream);

@@ -147,6 +147,16 @@ def test_bad_arguments_return_errors_not_crashes():
     assert b'multiple of 64' in lib.vlaser_last_error()
     assert lib.vlaser_gemm_tn_lds(P, P, P, 1002, 2048, 128, 1002, 2048, 2048, 0, None, 0, None) != 0
     assert b'rounded up to 8' in lib.vlaser_last_error()
+    # configuration codes: with otherwise valid arguments, a code the form does not have is refused by the launcher itself, before any launch
+    c = _lib.GemmArgs()
+    c.A, c.W, c.out = P, P, P
+    c.M, c.N, c.K, c.lda, c.ldw, c.ldo = 64, 64, 64, 64, 64, 64
+    for entry, code in ((lib.vlaser_gemm, 2100), (lib.vlaser_gemm, 7), (lib.vlaser_gemm_nn, 1564), (lib.vlaser_gemm_nn, 2100)):
+        c.force_bm = code
+        assert entry(0, ctypes.byref(c), None) != 0
+        assert str(code).encode() in lib.vlaser_last_error()
+    assert lib.vlaser_gemm_tn_lds(P, P, P, 128, 128, 64, 128, 128, 128, 1500, None, 0, None) != 0
+    assert b'1500' in lib.vlaser_last_error()
     # fused attention backward: cache row length not a multiple of 64 / more valid keys than cache rows
     assert lib.vlaser_attn_bwd(P, P, P, P, P, P, P, P, P, P, 70, 12, 2, 100, 0.1, 1, 70, 128, None) != 0
     assert b'bad geometry' in lib.vlaser_last_error()

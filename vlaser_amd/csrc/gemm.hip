@@ -16,9 +16,6 @@
 
 #define BN 128
 #define BK 64
-#ifndef GEMM_PD
-#define GEMM_PD 2
-#endif
 
 struct GemmP {
   VlaserGemmArgs a;
@@ -26,6 +23,12 @@ struct GemmP {
 };
 
 __device__ __forceinline__ int lds_off(int row, int slot) { return row * 128 + ((slot ^ (row & 7)) << 4); }
+
+// XCD-aware remap: block b runs on XCD b%8; give each XCD a contiguous chunk of the tile list (bijective form)
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
 
 template <int EPI>
 __device__ __forceinline__ void epilogue(const VlaserGemmArgs& a, int m, int n0, f32x4 v, f32x4 v2) {
@@ -576,9 +579,33 @@ __device__ __forceinline__ float epilogue_tile(const VlaserGemmArgs& a, int m_w,
   return ssq;
 }
 
+// The end of a workgroup of gemm_kernel and gemm_glds_kernel: this wave's tile (rows from m_w, columns from n_w; lane -> m = ... + (lane&15), n = ... + (lane>>4)*4 + reg)
+// leaves through the whole-tile form of epilogue EPI; false (nothing done) where EPI has none (F32 / PARTIAL / SWIGLU): the caller then goes fragment by fragment -- loops
+// that stay written out in both kernels, because behind a helper hipcc stops sharing their address arithmetic (+27 % instructions on the 256x256 PARTIAL kernel).
+// gemm_glds_kernel passes `scr`, its wave's LDS scratch for the row-contiguous stores, and tries the 16-byte SwiGLU stores itself first.  `ea` = the arguments already shifted to the workgroup's batch element: that shift stays written
+// out in both kernels -- behind any helper, or in here behind gemm_glds_kernel's barrier, hipcc allocates some of their kernels differently (profiles/gemm_dedup_ab.md).
+template <int EPI, int MT, int NT>
+__device__ __forceinline__ bool tile_epilogue(const VlaserGemmArgs& ea, int m_w, int n_w, int fr, int fq, f32x4 (&acc)[NT][MT], char* scr = nullptr) {
+  if constexpr (EPI == VL_EPI_NONE || EPI == VL_EPI_BIAS || EPI == VL_EPI_BIAS_GELU || EPI == VL_EPI_BIAS_LS_RES || EPI == VL_EPI_RES) {
+    epilogue_tile<EPI, MT, NT>(ea, m_w, n_w, fr, fq, acc, scr);
+    return true;
+  } else if constexpr (EPI == VL_EPI_QKV_ROPE) {
+    epilogue_tile_rope<MT, NT>(ea, m_w, n_w, fr, fq, acc);
+    return true;
+  } else if constexpr (EPI == VL_EPI_VIT_QKV) {
+    epilogue_tile_vit_qkv<MT, NT>(ea, m_w, n_w, fr, fq, acc);
+    return true;
+  } else if constexpr (EPI == VL_EPI_SWIGLU_BWD) {
+    epilogue_tile_swiglu_bwd<MT, NT>(ea, m_w, n_w, fr, fq, acc);
+    return true;
+  } else {
+    return false;
+  }
+}
+
 template <int EPI, int BM>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
-  constexpr int PD = GEMM_PD;                           // K-tiles in flight (register stages)
+  constexpr int PD = 2;                                 // K-tiles in flight (register stages)
   constexpr int WR = BM >= 64 ? 2 : 1, WC = 4 / WR;     // wave grid
   constexpr int WTM = BM / WR, WTN = BN / WC;           // wave tile
   constexpr int MT = WTM / 16, NT = WTN / 16;
@@ -589,13 +616,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave / WC, wc = wave % WC;
 
-  // XCD-aware remap: block b runs on XCD b%8; give each XCD a contiguous chunk of the tile list (bijective form)
-  const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int tile_m = bid % p.tiles_m, tile_n = bid / p.tiles_m;  // consecutive tiles share the weight panel
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int kc = a.K / (int)gridDim.y;                           // split-K slice of this block
@@ -685,38 +706,23 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
   for (int u = 0; u < PD - 1; ++u)
     if (kt0 + u < nk) kstep(kt0 + u, (u + 1) % PD);
 
-  // epilogue: lane -> m = ... + (lane&15), n = ... + (lane>>4)*4 + reg
   VlaserGemmArgs ea = a;      // batched: shift the output (bf16 / fp32 / partial) of this batch element
   if (bz > 0) {
     if (ea.out) ea.out = reinterpret_cast<char*>(ea.out) + (size_t)bz * a.o_bs * (EPI == VL_EPI_F32 ? 4 : 2);
     if (ea.out_f32) ea.out_f32 += (size_t)bz * a.o_bs;
     if (ea.res) ea.res = reinterpret_cast<const char*>(ea.res) + (size_t)bz * a.o_bs * 2;
   }
-  if constexpr (EPI == VL_EPI_NONE || EPI == VL_EPI_BIAS || EPI == VL_EPI_BIAS_GELU || EPI == VL_EPI_BIAS_LS_RES || EPI == VL_EPI_RES) {
-    epilogue_tile<EPI, MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc);
-    return;
-  }
-  if constexpr (EPI == VL_EPI_QKV_ROPE) {
-    epilogue_tile_rope<MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc);
-    return;
-  }
-  if constexpr (EPI == VL_EPI_VIT_QKV) {
-    epilogue_tile_vit_qkv<MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc);
-    return;
-  }
-  if constexpr (EPI == VL_EPI_SWIGLU_BWD) {
-    epilogue_tile_swiglu_bwd<MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc);
-    return;
-  }
+  if (!tile_epilogue<EPI, MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc)) {
 #pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int m = m0 + wr * WTM + mt * 16 + fr;
-    if constexpr (EPI == VL_EPI_SWIGLU || EPI == VL_EPI_QKV_ROPE) {
+    for (int mt = 0; mt < MT; ++mt) {
+      const int m = m0 + wr * WTM + mt * 16 + fr;
+      if constexpr (EPI == VL_EPI_SWIGLU) {
 #pragma unroll
-      for (int nt = 0; nt < NT; nt += 2) epilogue<EPI>(ea, m, n0 + wc * WTN + nt * 16 + fq * 4, acc[nt][mt], acc[nt + 1][mt]);
-    } else {
+        for (int nt = 0; nt < NT; nt += 2) epilogue<EPI>(ea, m, n0 + wc * WTN + nt * 16 + fq * 4, acc[nt][mt], acc[nt + 1][mt]);
+      } else {
 #pragma unroll
-      for (int nt = 0; nt < NT; ++nt) epilogue<EPI>(ea, m, n0 + wc * WTN + nt * 16 + fq * 4, acc[nt][mt], acc[nt][mt]);
+        for (int nt = 0; nt < NT; ++nt) epilogue<EPI>(ea, m, n0 + wc * WTN + nt * 16 + fq * 4, acc[nt][mt], acc[nt][mt]);
+      }
     }
   }
 }
@@ -752,6 +758,34 @@ extern "C" int vlaser_gemm_debug_read(long long* host) { return (int)hipMemcpyFr
 #endif
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
+// MFMA fragment of a k-major tile ([k][columns] rows of `row_bytes`, 16-byte slots swizzled on the source side -- see WKM below): the 8 k-values kr .. kr + 3, kr + 4 .. kr + 7
+// of column c0 + fr, through the transposing read.  Lower half: k-rows kr, upper: kr + 4 (same swizzle bits 0-1, 3).
+// KmajorLane = what a lane's k-row fixes of its two 8-byte reads, whatever the column tile.  gemm_tn_stag_kernel, whose kr never changes, computes it once in front of
+// its loop (left to the compiler's hoisting, its 128x256 tile allocates two registers fewer than it used to: the helpers must not move any kernel's allocation).
+struct KmajorLane { int kr, hb, key_lo, key_hi; };
+__device__ __forceinline__ KmajorLane kmajor_lane(int kr, int fr) {
+  return KmajorLane{kr, (fr & 1) * 8, 2 * ((kr & 3) | (((kr >> 3) & 1) << 2)), 2 * (((kr + 4) & 3) | ((((kr + 4) >> 3) & 1) << 2))};
+}
+__device__ __forceinline__ bf16x8 kmajor_frag(const char* tile, int row_bytes, const KmajorLane l, int c0, int fr) {
+  const int sl = (c0 >> 3) + ((fr & 3) >> 1);
+  typedef __attribute__((address_space(3))) s16x4_t* lds_p;
+  const char* plo = tile + l.kr * row_bytes + (((sl & ~15) | ((sl & 15) ^ l.key_lo)) << 4) + l.hb;
+  const char* phi = tile + (l.kr + 4) * row_bytes + (((sl & ~15) | ((sl & 15) ^ l.key_hi)) << 4) + l.hb;
+  union { s16x4_t h[2]; bf16x8 b; } u;
+  u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)plo);
+  u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)phi);
+  return u.b;
+}
+__device__ __forceinline__ bf16x8 kmajor_frag(const char* tile, int row_bytes, int kr, int c0, int fr) { return kmajor_frag(tile, row_bytes, kmajor_lane(kr, fr), c0, fr); }
+
+// MFMA fragment of half ks (32 k) of a staged tile for the 16 rows / columns from c0.  KMB = bytes per k-row of a k-major operand (kmajor_frag), 0 = row-major (128-byte
+// rows of 64 k, lds_off).  Both K-loops of gemm_glds_kernel read through here.
+template <int KMB>
+__device__ __forceinline__ bf16x8 tile_frag(const char* tile, int c0, int ks, int fr, int fq) {
+  if constexpr (KMB != 0) return kmajor_frag(tile, KMB, ks * 32 + 8 * fq + (fr >> 2), c0, fr);
+  else return as_bf16x8(*reinterpret_cast<const u32x4*>(tile + lds_off(c0 + fr, ks * 4 + fq)));
+}
+
 // WKM ("W k-major", the NN form out = A @ B): the second operand is stored [K][N] row-major -- a weight matrix exactly as the
 // forward keeps it, seen from its dgrad (dX = dY @ W).  Its K-tile is staged as [64 k][BNT n] (1 KiB pieces = 1024 / (2 BNT)
 // whole k-rows; XOR swizzle of the 16-byte slots on the source side again) and the MFMA fragments come out of LDS through the
@@ -765,11 +799,8 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // IFIRST: the refill of the stage read in the previous step is requested right behind the barrier, in FRONT of this step's fragment reads (r02 order) instead
 // of behind the first half's (r03).  With only two stages and HBM-cold weights (192x256, the training forward's gate/up) the extra half step of lead is
 // worth more than the reads it delays: 43.7 -> 38.7 us; every ring of three or more stages loses 5-13 % with it (tools/micro/gemm_epilogue_lab.py).
-// PRD (r05, LAB ONLY -- measured slower, see launch<>'s case 2100): PRD extra PRODUCER waves (one per SIMD) issue every LDS-DMA piece; the WM x WN compute waves only pass
-// the barrier, read fragments and issue MFMAs.  The idea: with no DMA at all the loop's compute side (fragment reads -> MFMAs, one barrier per K-step, 192x256 tile) runs at
-// 0.90 us per K-step = 1.8 PFLOP/s whatever the MFMA shape (tools/micro/mfma_shape_lab.hip, profiles/r05r_mfma_shape_lab.md), the product loop at 1.6.  A producer wave's
-// K-step: vmcnt for ITS pieces of tile kt -> barrier -> refill of the stage read in step kt-1.  What it showed: issuing pieces is serial PER WAVE, so fewer issuing waves
-// lengthen the step -- the 8 compute waves issuing 6 pieces each in parallel are the better arrangement.
+// Every compute wave issues its share of the pieces.  A lab with four dedicated producer waves (r05, profiles/r05s_producer_waves.md) was 12-16 % slower: piece issue is
+// serial per wave, so 8 waves x 6 pieces beat 4 x 12.
 // ASYM (r05): the W operand's ring is ONE STAGE DEEPER than the A operand's (NST + 1 against NST).  A two-stage ring has one tile in flight -- requested at step kt, needed at
 // kt + 1 -- and its step lasts as long as that round trip (192x256: 1.6 us against 0.9 us of fragment reads + MFMAs, profiles/r05r_mfma_shape_lab.md); a third full stage does
 // not fit 160 KB at these tile sizes, a third stage of the HBM-cold operand alone does (192x256: 2 x 24 + 3 x 32 = 144 KB): the weights get two steps of lead, the activations
@@ -781,13 +812,11 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // step is [barrier | reads(kt, h0) -> set A | MFMAs(kt-1, h1) from set B | reads(kt, h1) -> set B | MFMAs(kt, h0) from set A]: every read block is issued in front of an MFMA block
 // that does not depend on it.  Same accumulation order per accumulator (bit-identical).  The stage read in step kt-1 is still refilled in step kt: its pending reads (set B) are
 // retired by an explicit lgkmcnt(0) in front of the barrier -- long complete by then -- so no prefetch depth is lost (r02's version of the idea moved the barrier and lost a stage).
-template <int EPI, int BM, int BNT, int WM, int WN, int NST, bool WKM = false, bool AKM = false, bool IFIRST = GLDS_ISSUE_FIRST != 0, int PRD = 0, bool ASYM = false, bool SPREAD = false,
+template <int EPI, int BM, int BNT, int WM, int WN, int NST, bool WKM = false, bool AKM = false, bool IFIRST = GLDS_ISSUE_FIRST != 0, bool ASYM = false, bool SPREAD = false,
           bool PIPE = false>
-__global__ __launch_bounds__((WM * WN + PRD) * 64) void gemm_glds_kernel(GemmP p) {
-  static_assert(!(ASYM && PRD) && !(SPREAD && PRD), "one lab at a time");
-  static_assert(!PIPE || (PRD == 0 && !IFIRST), "PIPE: compute waves issue the pieces; the refill is spread or issued behind the first read block");
+__global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmP p) {
+  static_assert(!PIPE || !IFIRST, "PIPE: the refill is spread or issued behind the first read block");
   constexpr int NW = WM * WN;
-  constexpr int NWI = PRD ? PRD : NW;                    // waves that issue LDS-DMA pieces
   constexpr int WTM = BM / WM, WTN = BNT / WN;
   constexpr int MT = WTM / 16, NT = WTN / 16;
   constexpr int STAGE = (BM + BNT) * 128;               // bytes: A tile | W tile (row-major, 128 B = 64 k per row)
@@ -795,7 +824,7 @@ __global__ __launch_bounds__((WM * WN + PRD) * 64) void gemm_glds_kernel(GemmP p
   constexpr int WROWB = BNT * 2, WRPP = 1024 / WROWB, WSPR = BNT / 8;      // WKM: bytes per k-row, k-rows per piece, 16-byte slots per k-row
   constexpr int AROWB = BM * 2, ARPP = 1024 / AROWB, ASPR = BM / 8;        // AKM: the same for the A tile
   static_assert(!AKM || (WKM && (BM == 128 || BM == 256)), "AKM needs WKM and a power-of-two tile of >= 16 slots per k-row");
-  constexpr int PA = (NPA + NWI - 1) / NWI, PW = (NPW + NWI - 1) / NWI; // pieces per issuing wave per K-tile; an uneven split re-issues the last piece
+  constexpr int PA = (NPA + NW - 1) / NW, PW = (NPW + NW - 1) / NW;     // pieces per wave per K-tile; an uneven split re-issues the last piece
   constexpr int PIECES = PA + PW;                        // (same bytes to the same LDS address: benign) so every wave's vmcnt arithmetic is identical
   static_assert(NPA * 8 == BM && NPW * 8 == BNT, "tile rows must be multiples of 8");
   static_assert(NT % 2 == 0, "fused pair epilogues need an even number of 16-column tiles per wave");
@@ -803,15 +832,8 @@ __global__ __launch_bounds__((WM * WN + PRD) * 64) void gemm_glds_kernel(GemmP p
   const VlaserGemmArgs& a = p.a;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave / WN, wc = wave % WN;
-  const bool producer = PRD && wave >= NW;               // (wave-uniform)
-  const int iw = PRD ? wave - NW : wave;                 // index among the issuing waves (compute waves of a PRD kernel never use it)
-  const int nwg = gridDim.x;
   GEMM_STAMP(0)
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int tile_m = bid % p.tiles_m, tile_n = bid / p.tiles_m;
   const int m0 = tile_m * BM, n0 = tile_n * BNT;
   const int kc = a.K / (int)gridDim.y;
@@ -828,51 +850,56 @@ __global__ __launch_bounds__((WM * WN + PRD) * 64) void gemm_glds_kernel(GemmP p
 #pragma unroll
   for (int i = 0; i < PA; ++i) {
     if constexpr (AKM) {
-      const int krow = min(iw * PA + i, NPA - 1) * ARPP + lane / ASPR;
+      const int krow = min(wave * PA + i, NPA - 1) * ARPP + lane / ASPR;
       const int slot = (lane % ASPR) ^ (2 * ((krow & 3) | (((krow >> 3) & 1) << 2)));
       srcA[i] = A + (size_t)(kbase + krow) * a.lda + min(m0 + slot * 8, ((a.M + 7) & ~7) - 8);
     } else {
-      const int row = min(iw * PA + i, NPA - 1) * 8 + prow;
+      const int row = min(wave * PA + i, NPA - 1) * 8 + prow;
       srcA[i] = A + (size_t)min(m0 + row, a.M - 1) * a.lda + kbase + ((pslot ^ (row & 7)) << 3);
     }
   }
 #pragma unroll
   for (int i = 0; i < PW; ++i) {
     if constexpr (WKM) {
-      const int krow = min(iw * PW + i, NPW - 1) * WRPP + lane / WSPR;              // k-row of this lane inside the tile
+      const int krow = min(wave * PW + i, NPW - 1) * WRPP + lane / WSPR;              // k-row of this lane inside the tile
       const int slot = (lane % WSPR) ^ (2 * ((krow & 3) | (((krow >> 3) & 1) << 2)));    // logical 16-byte slot fetched into physical slot lane % WSPR
       srcW[i] = W + (size_t)(kbase + krow) * a.ldw + min(n0 + slot * 8, ((a.N + 7) & ~7) - 8);   // columns past N (chunk-aligned clamp) only feed dropped outputs
     } else {
-      const int row = min(iw * PW + i, NPW - 1) * 8 + prow;
+      const int row = min(wave * PW + i, NPW - 1) * 8 + prow;
       srcW[i] = W + (size_t)min(n0 + row, a.N - 1) * a.ldw + kbase + ((pslot ^ (row & 7)) << 3);
     }
   }
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;      // LDS byte address of the stage ring (low 32 bits of the generic pointer)
   constexpr int WRING = ASYM ? NST * BM * 128 : 0;      // ASYM: [NST A stages][NST + 1 W stages]; else [NST (A | W) stages]
-  auto issue_a = [&](int kt, int sa) {
-    const int ko = min(kt, nk - 1) * BK;                 // tiles past the end re-fetch the last one (never read)
-    const uint32_t base = lds0 + sa * (ASYM ? BM * 128 : STAGE);
-#pragma unroll
-    for (int i = 0; i < PA; ++i) glds16(srcA[i] + (AKM ? (size_t)ko * a.lda : (size_t)ko), __builtin_amdgcn_readfirstlane(base + min(iw * PA + i, NPA - 1) * 1024));
+  // the only place that turns a piece into a source address and an LDS destination: piece i of this wave's PA (PW) pieces of the A (W) tile at K offset ko into the stage at `base`
+  auto k_off = [&](int kt) { return min(kt, nk - 1) * BK; };      // tiles past the end re-fetch the last one (never read)
+  auto a_stage = [&](int sa) { return lds0 + sa * (ASYM ? BM * 128 : STAGE); };
+  auto w_stage = [&](int sw2) { return ASYM ? lds0 + WRING + sw2 * (BNT * 128) : lds0 + sw2 * STAGE + BM * 128; };
+  auto piece_a = [&](int i, int ko, uint32_t base) { glds16(srcA[i] + (AKM ? (size_t)ko * a.lda : (size_t)ko), __builtin_amdgcn_readfirstlane(base + min(wave * PA + i, NPA - 1) * 1024)); };
+  auto piece_w = [&](int i, int ko, uint32_t base) { glds16(srcW[i] + (WKM ? (size_t)ko * a.ldw : (size_t)ko), __builtin_amdgcn_readfirstlane(base + min(wave * PW + i, NPW - 1) * 1024)); };
+  // piece j of the PIECES of a refill (A pieces first, then W: the order the vmcnt arithmetic assumes): A tile kta into A stage sa, W tile ktw into W stage sw2
+  auto issue_piece = [&](int j, int kta, int sa, int ktw, int sw2) {
+    if (j < PA) piece_a(j, k_off(kta), a_stage(sa));
+    else piece_w(j - PA, k_off(ktw), w_stage(sw2));
   };
-  auto issue_w = [&](int kt, int sw) {
-    const int ko = min(kt, nk - 1) * BK;
-    const uint32_t base = ASYM ? lds0 + WRING + sw * (BNT * 128) : lds0 + sw * STAGE + BM * 128;
+  auto issue_a = [&](int kt, int sa) {
+    const int ko = k_off(kt);
+    const uint32_t base = a_stage(sa);
 #pragma unroll
-    for (int i = 0; i < PW; ++i) glds16(srcW[i] + (WKM ? (size_t)ko * a.ldw : (size_t)ko), __builtin_amdgcn_readfirstlane(base + min(iw * PW + i, NPW - 1) * 1024));
+    for (int i = 0; i < PA; ++i) piece_a(i, ko, base);
+  };
+  auto issue_w = [&](int kt, int sw2) {
+    const int ko = k_off(kt);
+    const uint32_t base = w_stage(sw2);
+#pragma unroll
+    for (int i = 0; i < PW; ++i) piece_w(i, ko, base);
   };
   auto issue_tile = [&](int kt, int st) { issue_a(kt, st); issue_w(kt, st); };
-  // piece j of a refill (A pieces first, then W: the order the vmcnt arithmetic assumes); kta / ktw and sa / sw as issue_a / issue_w take them
-  auto issue_piece = [&](int j, int kta, int sa, int ktw, int sw2) {
-    if (j < PA) {
-      const int ko = min(kta, nk - 1) * BK;
-      const uint32_t base = lds0 + sa * (ASYM ? BM * 128 : STAGE);
-      glds16(srcA[j] + (AKM ? (size_t)ko * a.lda : (size_t)ko), __builtin_amdgcn_readfirstlane(base + min(iw * PA + j, NPA - 1) * 1024));
-    } else {
-      const int i = j - PA, ko = min(ktw, nk - 1) * BK;
-      const uint32_t base = ASYM ? lds0 + WRING + sw2 * (BNT * 128) : lds0 + sw2 * STAGE + BM * 128;
-      glds16(srcW[i] + (WKM ? (size_t)ko * a.ldw : (size_t)ko), __builtin_amdgcn_readfirstlane(base + min(iw * PW + i, NPW - 1) * 1024));
-    }
+  // the refill of step kt as one burst: the stage(s) read in step kt - 1 (stn; ASYM: A stage stn, W stage swn) take the tiles NST - 1 (ASYM, W: NST) ahead.  (The
+  // arguments by reference and the two call sites of the plain loop are the form that leaves every kernel's register allocation where it was: profiles/gemm_dedup_ab.md.)
+  auto refill = [&](const int& kt, const int& stn, const int& swn) {
+    if constexpr (ASYM) { issue_a(kt + NST - 1, stn); issue_w(kt + NST, swn); }
+    else issue_tile(kt + NST - 1, stn);
   };
 
   f32x4 acc[NT][MT];
@@ -881,11 +908,9 @@ __global__ __launch_bounds__((WM * WN + PRD) * 64) void gemm_glds_kernel(GemmP p
 #pragma unroll
     for (int j = 0; j < MT; ++j) acc[i][j] = f32x4{0, 0, 0, 0};
 
-  if (!PRD || producer) {
 #pragma unroll
-    for (int st = 0; st < NST - 1; ++st) issue_tile(st, st);
-    if constexpr (ASYM) issue_w(NST - 1, NST - 1);
-  }
+  for (int st = 0; st < NST - 1; ++st) issue_tile(st, st);
+  if constexpr (ASYM) issue_w(NST - 1, NST - 1);
   GEMM_STAMP(1)
   const int fr = lane & 15, fq = lane >> 4;
   int st = 0;                                            // stage of tile kt (ASYM: of its A tile)
@@ -893,39 +918,9 @@ __global__ __launch_bounds__((WM * WN + PRD) * 64) void gemm_glds_kernel(GemmP p
   if constexpr (PIPE) {
     auto read_frags = [&](int ks, const char* As, const char* Ws, bf16x8 (&fa)[MT], bf16x8 (&fw)[NT]) __attribute__((always_inline)) {
 #pragma unroll
-      for (int t = 0; t < MT; ++t) {
-        if constexpr (AKM) {
-          const int kr = ks * 32 + 8 * fq + (fr >> 2), c0 = wr * WTM + t * 16;
-          const int sl = (c0 >> 3) + ((fr & 3) >> 1), hb = (fr & 1) * 8;
-          const int key_lo = 2 * ((kr & 3) | (((kr >> 3) & 1) << 2)), key_hi = 2 * (((kr + 4) & 3) | ((((kr + 4) >> 3) & 1) << 2));
-          typedef __attribute__((address_space(3))) s16x4_t* lds_p;
-          const char* plo = As + kr * AROWB + (((sl & ~15) | ((sl & 15) ^ key_lo)) << 4) + hb;
-          const char* phi = As + (kr + 4) * AROWB + (((sl & ~15) | ((sl & 15) ^ key_hi)) << 4) + hb;
-          union { s16x4_t h[2]; bf16x8 b; } u;
-          u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)plo);
-          u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)phi);
-          fa[t] = u.b;
-        } else {
-          fa[t] = as_bf16x8(*reinterpret_cast<const u32x4*>(As + lds_off(wr * WTM + t * 16 + fr, ks * 4 + fq)));
-        }
-      }
+      for (int t = 0; t < MT; ++t) fa[t] = tile_frag<AKM ? AROWB : 0>(As, wr * WTM + t * 16, ks, fr, fq);
 #pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        if constexpr (WKM) {
-          const int kr = ks * 32 + 8 * fq + (fr >> 2), c0 = wc * WTN + t * 16;
-          const int sl = (c0 >> 3) + ((fr & 3) >> 1), hb = (fr & 1) * 8;
-          const int key_lo = 2 * ((kr & 3) | (((kr >> 3) & 1) << 2)), key_hi = 2 * (((kr + 4) & 3) | ((((kr + 4) >> 3) & 1) << 2));
-          typedef __attribute__((address_space(3))) s16x4_t* lds_p;
-          const char* plo = Ws + kr * WROWB + (((sl & ~15) | ((sl & 15) ^ key_lo)) << 4) + hb;
-          const char* phi = Ws + (kr + 4) * WROWB + (((sl & ~15) | ((sl & 15) ^ key_hi)) << 4) + hb;
-          union { s16x4_t h[2]; bf16x8 b; } u;
-          u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)plo);
-          u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)phi);
-          fw[t] = u.b;
-        } else {
-          fw[t] = as_bf16x8(*reinterpret_cast<const u32x4*>(Ws + lds_off(wc * WTN + t * 16 + fr, ks * 4 + fq)));
-        }
-      }
+      for (int t = 0; t < NT; ++t) fw[t] = tile_frag<WKM ? WROWB : 0>(Ws, wc * WTN + t * 16, ks, fr, fq);
     };
     // one block of MT x NT MFMAs; `blk` = 0 / 1: first / second block of the step (the spread refill counts MFMAs over both); kt / stn / swn: the step whose refill rides here
     auto mfma_block = [&](const bf16x8 (&fa)[MT], const bf16x8 (&fw)[NT], int blk, bool refill, int kt, int stn, int swn) __attribute__((always_inline)) {
@@ -945,10 +940,6 @@ __global__ __launch_bounds__((WM * WN + PRD) * 64) void gemm_glds_kernel(GemmP p
           }
         }
     };
-    auto refill_burst = [&](int kt, int stn, int swn) __attribute__((always_inline)) {
-      if constexpr (ASYM) { issue_a(kt + NST - 1, stn); issue_w(kt + NST, swn); }
-      else issue_tile(kt + NST - 1, stn);
-    };
     bf16x8 faA[MT], fwA[NT], faB[MT], fwB[NT];
     for (int kt = 0; kt < nk; ++kt) {
       if constexpr (ASYM) wait_vmcnt<PA * (NST - 2) + PW * (NST - 1)>();
@@ -963,7 +954,7 @@ __global__ __launch_bounds__((WM * WN + PRD) * 64) void gemm_glds_kernel(GemmP p
       read_frags(0, As, Ws, faA, fwA);
       // the refill of this step: spread over the step's two MFMA blocks, or -- burst form, and ALWAYS in step 0, which has no first block -- in one piece behind the first read
       // block, in the order the vmcnt arithmetic assumes (A pieces, then W pieces)
-      if (!SPREAD || kt == 0) refill_burst(kt, stn, swn);
+      if (!SPREAD || kt == 0) refill(kt, stn, swn);
       if (kt > 0) mfma_block(faB, fwB, 0, SPREAD, kt, stn, swn);
       read_frags(1, As, Ws, faB, fwB);
       mfma_block(faA, fwA, 1, SPREAD && kt > 0, kt, stn, swn);
@@ -975,67 +966,26 @@ __global__ __launch_bounds__((WM * WN + PRD) * 64) void gemm_glds_kernel(GemmP p
   {
   for (int kt = 0; kt < nk; ++kt) {
     if constexpr (ASYM) wait_vmcnt<PA * (NST - 2) + PW * (NST - 1)>();
-    else if (!PRD || producer) wait_vmcnt<PIECES * (NST - 2)>();      // this wave's pieces of tile kt have landed (younger tiles may fly)
+    else wait_vmcnt<PIECES * (NST - 2)>();               // this wave's pieces of tile kt have landed (younger tiles may fly)
     __builtin_amdgcn_s_barrier();                        // ... and everyone else's; also: all waves are done reading stage kt-1
     GEMM_STAMP(2 + kt)
     int stn = st + NST - 1; if (stn >= NST) stn -= NST;  // = (kt-1) % NST: the stage read in the previous step
-    if constexpr (PRD > 0) {
-      if (producer) {
-        issue_tile(kt + NST - 1, stn);
-        if (++st == NST) st = 0;
-        continue;
-      }
-    }
     const char* As = smem + st * (ASYM ? BM * 128 : STAGE);
     const char* Ws = ASYM ? smem + WRING + sw * (BNT * 128) : As + BM * 128;
     [[maybe_unused]] int swn = sw + NST; if (swn >= NST + 1) swn -= NST + 1;      // ASYM: = (kt - 1) % (NST + 1): the W stage read in the previous step
-    auto refill = [&]() {
-      if constexpr (ASYM) { issue_a(kt + NST - 1, stn); issue_w(kt + NST, swn); }
-      else issue_tile(kt + NST - 1, stn);
-    };
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8 fa[MT], fw[NT];
       // (r03) the refill of stage kt-1 is issued BEHIND the first half's fragment reads: an LDS-DMA piece costs ~100-185 issue cycles
       // (MI355X_MICROARCH.md), and in front of the reads the whole K-step sat behind PIECES of them before its first ds_read went out
-      if constexpr (PRD == 0 && !SPREAD) {
-        if (ks == 1 && !IFIRST) refill();
-        if (ks == 0 && IFIRST) refill();
+      if constexpr (!SPREAD) {
+        if (ks == 1 && !IFIRST) refill(kt, stn, swn);
+        if (ks == 0 && IFIRST) refill(kt, stn, swn);
       }
 #pragma unroll
-      for (int t = 0; t < MT; ++t) {
-        if constexpr (AKM) {
-          const int kr = ks * 32 + 8 * fq + (fr >> 2), c0 = wr * WTM + t * 16;
-          const int sl = (c0 >> 3) + ((fr & 3) >> 1), hb = (fr & 1) * 8;
-          const int key_lo = 2 * ((kr & 3) | (((kr >> 3) & 1) << 2)), key_hi = 2 * (((kr + 4) & 3) | ((((kr + 4) >> 3) & 1) << 2));
-          typedef __attribute__((address_space(3))) s16x4_t* lds_p;
-          const char* plo = As + kr * AROWB + (((sl & ~15) | ((sl & 15) ^ key_lo)) << 4) + hb;
-          const char* phi = As + (kr + 4) * AROWB + (((sl & ~15) | ((sl & 15) ^ key_hi)) << 4) + hb;
-          union { s16x4_t h[2]; bf16x8 b; } u;
-          u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)plo);
-          u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)phi);
-          fa[t] = u.b;
-        } else {
-          fa[t] = as_bf16x8(*reinterpret_cast<const u32x4*>(As + lds_off(wr * WTM + t * 16 + fr, ks * 4 + fq)));
-        }
-      }
+      for (int t = 0; t < MT; ++t) fa[t] = tile_frag<AKM ? AROWB : 0>(As, wr * WTM + t * 16, ks, fr, fq);
 #pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        if constexpr (WKM) {
-          const int kr = ks * 32 + 8 * fq + (fr >> 2), c0 = wc * WTN + t * 16;      // lower half: k-rows kr, upper: kr + 4 (same swizzle bits 0-1, 3)
-          const int sl = (c0 >> 3) + ((fr & 3) >> 1), hb = (fr & 1) * 8;
-          const int key_lo = 2 * ((kr & 3) | (((kr >> 3) & 1) << 2)), key_hi = 2 * (((kr + 4) & 3) | ((((kr + 4) >> 3) & 1) << 2));
-          typedef __attribute__((address_space(3))) s16x4_t* lds_p;
-          const char* plo = Ws + kr * WROWB + (((sl & ~15) | ((sl & 15) ^ key_lo)) << 4) + hb;
-          const char* phi = Ws + (kr + 4) * WROWB + (((sl & ~15) | ((sl & 15) ^ key_hi)) << 4) + hb;
-          union { s16x4_t h[2]; bf16x8 b; } u;
-          u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)plo);
-          u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)phi);
-          fw[t] = u.b;
-        } else {
-          fw[t] = as_bf16x8(*reinterpret_cast<const u32x4*>(Ws + lds_off(wc * WTN + t * 16 + fr, ks * 4 + fq)));
-        }
-      }
+      for (int t = 0; t < NT; ++t) fw[t] = tile_frag<WKM ? WROWB : 0>(Ws, wc * WTN + t * 16, ks, fr, fq);
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -1058,9 +1008,8 @@ __global__ __launch_bounds__((WM * WN + PRD) * 64) void gemm_glds_kernel(GemmP p
   }
   GEMM_STAMP(36)
   wait_vmcnt<0>();                                       // drain the clamped look-ahead tiles before the block retires
-  if constexpr (PRD > 0) { if (producer) return; }       // (a terminated wave leaves the barrier's count: the epilogue's barrier below completes once every producer has drained and left)
 
-  VlaserGemmArgs ea = a;
+  VlaserGemmArgs ea = a;      // batched: shift the output (bf16 / fp32 / partial) of this batch element
   if (bz > 0) {
     if (ea.out) ea.out = reinterpret_cast<char*>(ea.out) + (size_t)bz * a.o_bs * (EPI == VL_EPI_F32 ? 4 : 2);
     if (ea.out_f32) ea.out_f32 += (size_t)bz * a.o_bs;
@@ -1072,56 +1021,32 @@ __global__ __launch_bounds__((WM * WN + PRD) * 64) void gemm_glds_kernel(GemmP p
     __builtin_amdgcn_s_barrier();                        // (each wave drained its own LDS-DMA pieces above: nothing lands in the ring any more)
     scr = smem + wave * EpiScratch<MT, NT>::BYTES;
   }
+  GEMM_STAMP(37)
   if constexpr (EPI == VL_EPI_NONE && AKM) {           // the weight-gradient form: optionally this wave's share of the gradient norm (one slot per wave,
-    GEMM_STAMP(37)
-    const float ssq = epilogue_tile<EPI, MT, NT, true>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc, scr);      // no atomics: the caller sums the slots in order)
+    const float ssq = epilogue_tile<EPI, MT, NT, true>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc, scr);
     if (a.sumsq_part) {
       const float w = wave_sum(ssq);
       if (lane == 0) a.sumsq_part[(size_t)(blockIdx.x + gridDim.x * blockIdx.z) * NW + wave] = w;
     }
-    GEMM_STAMP(38)
-    return;
-  }
-  if constexpr (EPI == VL_EPI_NONE || EPI == VL_EPI_BIAS || EPI == VL_EPI_BIAS_GELU || EPI == VL_EPI_BIAS_LS_RES || EPI == VL_EPI_RES) {
-    GEMM_STAMP(37)
-    epilogue_tile<EPI, MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc, scr);
-    GEMM_STAMP(38)
-    return;
-  }
-  if constexpr (EPI == VL_EPI_QKV_ROPE) {
-    GEMM_STAMP(37)
-    epilogue_tile_rope<MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc);
-    GEMM_STAMP(38)
-    return;
-  }
-  if constexpr (EPI == VL_EPI_VIT_QKV) {
-    GEMM_STAMP(37)
-    epilogue_tile_vit_qkv<MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc);
-    GEMM_STAMP(38)
-    return;
-  }
-  if constexpr (EPI == VL_EPI_SWIGLU_BWD) {
-    GEMM_STAMP(37)
-    epilogue_tile_swiglu_bwd<MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc);
-    GEMM_STAMP(38)
-    return;
-  }
-  GEMM_STAMP(37)
-  if constexpr (EPI == VL_EPI_SWIGLU) {
-    if (epilogue_tile_swiglu<MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc)) {
-      GEMM_STAMP(38)
-      return;
+  } else {
+    if constexpr (EPI == VL_EPI_SWIGLU) {                // 16-byte stores where the tile allows them
+      if (epilogue_tile_swiglu<MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc)) {
+        GEMM_STAMP(38)
+        return;
+      }
     }
-  }
+    if (!tile_epilogue<EPI, MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc, scr)) {
 #pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int m = m0 + wr * WTM + mt * 16 + fr;
-    if constexpr (EPI == VL_EPI_SWIGLU || EPI == VL_EPI_QKV_ROPE) {
+      for (int mt = 0; mt < MT; ++mt) {
+        const int m = m0 + wr * WTM + mt * 16 + fr;
+        if constexpr (EPI == VL_EPI_SWIGLU) {
 #pragma unroll
-      for (int nt = 0; nt < NT; nt += 2) epilogue<EPI>(ea, m, n0 + wc * WTN + nt * 16 + fq * 4, acc[nt][mt], acc[nt + 1][mt]);
-    } else {
+          for (int nt = 0; nt < NT; nt += 2) epilogue<EPI>(ea, m, n0 + wc * WTN + nt * 16 + fq * 4, acc[nt][mt], acc[nt + 1][mt]);
+        } else {
 #pragma unroll
-      for (int nt = 0; nt < NT; ++nt) epilogue<EPI>(ea, m, n0 + wc * WTN + nt * 16 + fq * 4, acc[nt][mt], acc[nt][mt]);
+          for (int nt = 0; nt < NT; ++nt) epilogue<EPI>(ea, m, n0 + wc * WTN + nt * 16 + fq * 4, acc[nt][mt], acc[nt][mt]);
+        }
+      }
     }
   }
   GEMM_STAMP(38)
@@ -1153,12 +1078,7 @@ __global__ __launch_bounds__(512) void gemm_tn_stag_kernel(GemmP p) {
   const VlaserGemmArgs& a = p.a;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave / WN, wc = wave % WN;
-  const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int tile_m = bid % p.tiles_m, tile_n = bid / p.tiles_m;
   const int m0 = tile_m * BM, n0 = tile_n * BNT;
   const bf16_t* A = reinterpret_cast<const bf16_t*>(a.A);
@@ -1193,10 +1113,7 @@ __global__ __launch_bounds__(512) void gemm_tn_stag_kernel(GemmP p) {
 #pragma unroll
     for (int j = 0; j < MT; ++j) acc[i][j] = f32x4{0, 0, 0, 0};
   const int fr = lane & 15, fq = lane >> 4;
-  // fragment addresses inside a buffer (k-row kr and kr + 4 of the 32 staged; swizzle as in gemm_glds_kernel's k-major operands)
-  const int kr = 8 * fq + (fr >> 2), hb = (fr & 1) * 8;
-  const int key_lo = 2 * ((kr & 3) | (((kr >> 3) & 1) << 2)), key_hi = 2 * (((kr + 4) & 3) | ((((kr + 4) >> 3) & 1) << 2));
-  typedef __attribute__((address_space(3))) s16x4_t* lds_p;
+  const KmajorLane kr = kmajor_lane(8 * fq + (fr >> 2), fr);      // fragments: k-rows kr and kr + 4 of the 32 staged, read like gemm_glds_kernel's k-major operands
   issue_tile(0, 0);
   issue_tile(1, 1);
   wait_vmcnt<PIECES>();                                  // tile 0 has landed
@@ -1212,25 +1129,9 @@ __global__ __launch_bounds__(512) void gemm_tn_stag_kernel(GemmP p) {
     const char* Ws = As + ABYTES;
     bf16x8 fa[MT], fw[NT];
 #pragma unroll
-    for (int t = 0; t < MT; ++t) {
-      const int c0 = wr * WTM + t * 16, sl = (c0 >> 3) + ((fr & 3) >> 1);
-      const char* plo = As + kr * AROWB + (((sl & ~15) | ((sl & 15) ^ key_lo)) << 4) + hb;
-      const char* phi = As + (kr + 4) * AROWB + (((sl & ~15) | ((sl & 15) ^ key_hi)) << 4) + hb;
-      union { s16x4_t h[2]; bf16x8 v; } u;
-      u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)plo);
-      u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)phi);
-      fa[t] = u.v;
-    }
+    for (int t = 0; t < MT; ++t) fa[t] = kmajor_frag(As, AROWB, kr, wr * WTM + t * 16, fr);
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int c0 = wc * WTN + t * 16, sl = (c0 >> 3) + ((fr & 3) >> 1);
-      const char* plo = Ws + kr * WROWB + (((sl & ~15) | ((sl & 15) ^ key_lo)) << 4) + hb;
-      const char* phi = Ws + (kr + 4) * WROWB + (((sl & ~15) | ((sl & 15) ^ key_hi)) << 4) + hb;
-      union { s16x4_t h[2]; bf16x8 v; } u;
-      u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)plo);
-      u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(uint32_t)(uintptr_t)phi);
-      fw[t] = u.v;
-    }
+    for (int t = 0; t < NT; ++t) fw[t] = kmajor_frag(Ws, WROWB, kr, wc * WTN + t * 16, fr);
     __builtin_amdgcn_sched_barrier(0);
     wait_vmcnt<PIECES>();                                // tile ph+1 has landed (this wave's pieces); tile ph+2 may still fly
     __builtin_amdgcn_s_barrier();
@@ -1275,23 +1176,27 @@ static int launch_tn_stag(const VlaserGemmArgs* args, hipStream_t stream) {
   return 0;
 }
 
-template <int EPI, int BM, int BNT, int WM, int WN, int NST, bool WKM = false, bool AKM = false, bool IFIRST = GLDS_ISSUE_FIRST != 0, int PRD = 0, bool ASYM = false, bool SPREAD = false,
-          bool PIPE = false>
+// An LDS-DMA configuration on the host side: tile BM x BNT, wave grid WM x WN, ring depth NST, the operand forms, and a word of these flags (each is the kernel template
+// parameter of the same name: see gemm_glds_kernel's header comment).  No flags = the plain loop with the refill as one burst; the lab build -DGLDS_ISSUE_FIRST=1
+// (tools/micro/gemm_epilogue_lab.py) turns exactly those configurations into the issue-first order.
+enum : int { IFIRST = 1, ASYM = 2, SPREAD = 4, PIPE = 8 };
+template <int EPI, int BM, int BNT, int WM, int WN, int NST, bool WKM, bool AKM, int FLAGS = 0>
 static int launch_glds(const VlaserGemmArgs* args, hipStream_t stream, int splits) {
+  constexpr bool ASYM_ = (FLAGS & ASYM) != 0;
+  constexpr auto kernel = gemm_glds_kernel<EPI, BM, BNT, WM, WN, NST, WKM, AKM, (FLAGS & IFIRST) != 0 || (FLAGS == 0 && GLDS_ISSUE_FIRST != 0), ASYM_, (FLAGS & SPREAD) != 0, (FLAGS & PIPE) != 0>;
   GemmP p;
   p.a = *args;
   p.tiles_m = (args->M + BM - 1) / BM;
   p.tiles_n = (args->N + BNT - 1) / BNT;
-  constexpr int lds = NST * (BM + BNT) * 128 + (ASYM ? BNT * 128 : 0);
+  constexpr int lds = NST * (BM + BNT) * 128 + (ASYM_ ? BNT * 128 : 0);
   static_assert(lds <= 160 * 1024, "stage ring exceeds the 160 KiB LDS of a CU");
   if (args->sumsq_part) {
     VL_CHECK(EPI == VL_EPI_NONE && AKM && splits == 1, "sumsq_part: only the TN weight-gradient form (vlaser_gemm_tn_lds) sums its output's squares");
     const long long need = (long long)p.tiles_m * p.tiles_n * (args->batch > 1 ? args->batch : 1) * WM * WN;
     VL_CHECK(args->sumsq_cap >= need, "sumsq_part: %d slots given, this launch writes %lld (workgroups x waves)", args->sumsq_cap, need);
   }
-  if (int rc = set_max_lds_once(gemm_glds_kernel<EPI, BM, BNT, WM, WN, NST, WKM, AKM, IFIRST, PRD, ASYM, SPREAD, PIPE>, lds)) return rc;
-  hipLaunchKernelGGL((gemm_glds_kernel<EPI, BM, BNT, WM, WN, NST, WKM, AKM, IFIRST, PRD, ASYM, SPREAD, PIPE>), dim3(p.tiles_m * p.tiles_n, splits, args->batch > 1 ? args->batch : 1),
-                     dim3((WM * WN + PRD) * 64), lds, stream, p);
+  if (int rc = set_max_lds_once(kernel, lds)) return rc;
+  hipLaunchKernelGGL(kernel, dim3(p.tiles_m * p.tiles_n, splits, args->batch > 1 ? args->batch : 1), dim3(WM * WN * 64), lds, stream, p);
   VL_LAUNCH_CHECK();
   return 0;
 }
@@ -1368,16 +1273,17 @@ static int launch(const VlaserGemmArgs* args, hipStream_t stream) {
       }
     }
   }
-  // LDS-DMA pipeline configurations: 1100 = 128x128 / 4 stages, 1200 = 128x256 / 3, 1300 = 256x256 / 2, 1500 = 64x128 / 4 (8 waves each), 1440 = 144x128 / 4 (6 waves)
+  // The configuration codes (the table at force_bm in include/vlaser_hip.h lists them once); a code this form or epilogue does not have falls out of its switch and is refused
+  // below, before any launch.
   if constexpr (AKM) {
     switch (bm) {
       // (r05: neither the asymmetric ring nor the spread refill helps the TN form -- both operands are activations / gradients out of L2, and its 256x256 tile lost 3-6 % with
       // the pieces between the MFMAs: profiles/r05z_spread_lab.md -- so it keeps the r04 rings)
       case 1100: return launch_glds<EPI, 128, 128, 2, 4, 4, true, true>(args, stream, splits);
-      case 1110: return launch_glds<EPI, 128, 128, 2, 4, 4, true, true, false, 0, false, false, true>(args, stream, splits);      // lab (r06): PIPE on the TN tiles -- the step moved by 0.05 ms: not the default
+      case 1110: return launch_glds<EPI, 128, 128, 2, 4, 4, true, true, PIPE>(args, stream, splits);      // lab (r06): PIPE on the TN tiles -- the step moved by 0.05 ms: not the default
       case 1105: return launch_glds<EPI, 128, 128, 2, 4, 5, true, true>(args, stream, splits);
       case 1200: return launch_glds<EPI, 128, 256, 2, 4, 3, true, true>(args, stream, splits);
-      case 1210: return launch_glds<EPI, 128, 256, 2, 4, 3, true, true, false, 0, false, false, true>(args, stream, splits);
+      case 1210: return launch_glds<EPI, 128, 256, 2, 4, 3, true, true, PIPE>(args, stream, splits);
       case 1300: return launch_glds<EPI, 256, 256, 2, 4, 2, true, true>(args, stream, splits);
       // r04: two staggered wave groups over a ring of four 32-deep buffers (gemm_tn_stag_kernel)
       case 1340: if constexpr (EPI == VL_EPI_NONE) return launch_tn_stag<256, 256>(args, stream); break;
@@ -1385,7 +1291,7 @@ static int launch(const VlaserGemmArgs* args, hipStream_t stream) {
       case 1140: if constexpr (EPI == VL_EPI_NONE) return launch_tn_stag<128, 128>(args, stream); break;
       default: break;
     }
-    vlaser_set_error("vlaser_gemm_tn_lds: force_cfg must be 0 or 1100 / 1110 / 1105 / 1200 / 1210 / 1300 / 1140 / 1240 / 1340 (got %d)", bm);
+    vlaser_set_error("vlaser_gemm_tn_lds: force_cfg = %d is not a configuration code of the TN form (see the table at force_bm in include/vlaser_hip.h)", bm);
     return -1;
   }
   switch (bm) {
@@ -1394,49 +1300,46 @@ static int launch(const VlaserGemmArgs* args, hipStream_t stream) {
     // r06: fragment reads pipelined across the K-step's barrier (PIPE: bit-identical; whole launches -4.1 ... -5.0 % on 144x128, -2.5 ... -5.3 % on 64x128, -6.1 ... -6.3 % on 64x64,
     // -4.3 ... -6.6 % on 192x256, noise on 128x128 / 128x256 which keep the plain loop -- profiles/r06o_pipe_ab.md); 1442 / 1502 / 1566 / 1902 = the r05 defaults for same-box A/B
     // (through force_bm)
-    case 1100: return launch_glds<EPI, 128, 128, 2, 4, 4, WKM, false, false, 0, false, true>(args, stream, splits);
-    case 1110: return launch_glds<EPI, 128, 128, 2, 4, 4, WKM, false, false, 0, false, true, true>(args, stream, splits);      // lab: PIPE on 128x128 (-2.4 ... +3.6 %: noise; not the default)
-    case 1101: return launch_glds<EPI, 128, 128, 2, 4, 4, WKM>(args, stream, splits);
-    case 1200: return launch_glds<EPI, 128, 256, 2, 4, 3, WKM, false, false, 0, false, true>(args, stream, splits);
-    case 1210: return launch_glds<EPI, 128, 256, 2, 4, 3, WKM, false, false, 0, false, true, true>(args, stream, splits);      // lab: PIPE on 128x256 (-2.2 ... +2.0 %: noise; not the default)
-    case 1201: return launch_glds<EPI, 128, 256, 2, 4, 3, WKM>(args, stream, splits);
+    case 1100: return launch_glds<EPI, 128, 128, 2, 4, 4, WKM, false, SPREAD>(args, stream, splits);
+    case 1110: return launch_glds<EPI, 128, 128, 2, 4, 4, WKM, false, SPREAD | PIPE>(args, stream, splits);      // lab: PIPE on 128x128 (-2.4 ... +3.6 %: noise; not the default)
+    case 1101: return launch_glds<EPI, 128, 128, 2, 4, 4, WKM, false>(args, stream, splits);
+    case 1200: return launch_glds<EPI, 128, 256, 2, 4, 3, WKM, false, SPREAD>(args, stream, splits);
+    case 1210: return launch_glds<EPI, 128, 256, 2, 4, 3, WKM, false, SPREAD | PIPE>(args, stream, splits);      // lab: PIPE on 128x256 (-2.2 ... +2.0 %: noise; not the default)
+    case 1201: return launch_glds<EPI, 128, 256, 2, 4, 3, WKM, false>(args, stream, splits);
     // r05: the two-stage rings carry a THIRD stage for the W operand alone (ASYM: weights two steps ahead, activations one; 256x256: 2 x 32 + 3 x 32 = 160 KB, 192x256: 144 KB):
     // bit-identical, 3408 x 8192 x 3584 193.9 -> 168.6 us, the SFT forward's gate/up 42.7 -> 37.2 us (tools/micro/asym_ring_lab.py, profiles/r05t_asym_ring_lab.md)
-    case 1300: return launch_glds<EPI, 256, 256, 2, 4, 2, WKM, false, false, 0, true, true>(args, stream, splits);
-    case 1304: return launch_glds<EPI, 256, 256, 2, 4, 2, WKM, false, false, 0, true>(args, stream, splits);      // lab: asymmetric ring, refill as one burst
-    case 1310: if constexpr (!WKM) return launch_glds<EPI, 256, 256, 2, 4, 2, false, false, false, 0, true, true, true>(args, stream, splits); break;      // lab (r06): PIPE on 256x256, NT only (the NN form's transposing reads spill at 256 registers)
-    case 1301: return launch_glds<EPI, 256, 256, 2, 4, 2, WKM, false, true>(args, stream, splits);      // lab: the two-stage 256x256 ring with the refill requested first
-    case 1302: return launch_glds<EPI, 256, 256, 2, 4, 2, WKM>(args, stream, splits);                   // lab: the r02-r04 two-stage ring
-    case 1500: return launch_glds<EPI, 64, 128, 2, 4, 4, WKM, false, false, 0, false, true, true>(args, stream, splits);
-    case 1502: return launch_glds<EPI, 64, 128, 2, 4, 4, WKM, false, false, 0, false, true>(args, stream, splits);
-    case 1501: return launch_glds<EPI, 64, 128, 2, 4, 4, WKM>(args, stream, splits);
-    case 1440: return launch_glds<EPI, 144, 128, 3, 2, 4, WKM, false, false, 0, false, true, true>(args, stream, splits);
-    case 1442: return launch_glds<EPI, 144, 128, 3, 2, 4, WKM, false, false, 0, false, true>(args, stream, splits);
-    case 1441: return launch_glds<EPI, 144, 128, 3, 2, 4, WKM>(args, stream, splits);
+    case 1300: return launch_glds<EPI, 256, 256, 2, 4, 2, WKM, false, ASYM | SPREAD>(args, stream, splits);
+    case 1304: return launch_glds<EPI, 256, 256, 2, 4, 2, WKM, false, ASYM>(args, stream, splits);      // lab: asymmetric ring, refill as one burst
+    case 1310: if constexpr (!WKM) return launch_glds<EPI, 256, 256, 2, 4, 2, false, false, ASYM | SPREAD | PIPE>(args, stream, splits); break;      // lab (r06): PIPE on 256x256, NT only (the NN form's transposing reads spill at 256 registers)
+    case 1301: return launch_glds<EPI, 256, 256, 2, 4, 2, WKM, false, IFIRST>(args, stream, splits);      // lab: the two-stage 256x256 ring with the refill requested first
+    case 1302: return launch_glds<EPI, 256, 256, 2, 4, 2, WKM, false>(args, stream, splits);                   // lab: the r02-r04 two-stage ring
+    case 1500: return launch_glds<EPI, 64, 128, 2, 4, 4, WKM, false, SPREAD | PIPE>(args, stream, splits);
+    case 1502: return launch_glds<EPI, 64, 128, 2, 4, 4, WKM, false, SPREAD>(args, stream, splits);
+    case 1501: return launch_glds<EPI, 64, 128, 2, 4, 4, WKM, false>(args, stream, splits);
+    case 1440: return launch_glds<EPI, 144, 128, 3, 2, 4, WKM, false, SPREAD | PIPE>(args, stream, splits);
+    case 1442: return launch_glds<EPI, 144, 128, 3, 2, 4, WKM, false, SPREAD>(args, stream, splits);
+    case 1441: return launch_glds<EPI, 144, 128, 3, 2, 4, WKM, false>(args, stream, splits);
     // r03: deeper rings / smaller tiles for the latency-bound single-round shapes (a K-step of the 64x128 tile takes ~0.38 us with 3 tiles in flight:
     // the LDS-DMA round trip under load is ~1.1 us, so the bytes in flight per CU, not the MFMA pipe, set the rate)
-    case 1506: return launch_glds<EPI, 64, 128, 2, 4, 6, WKM>(args, stream, splits);
-    case 1105: return launch_glds<EPI, 128, 128, 2, 4, 5, WKM>(args, stream, splits);
-    case 1564: if constexpr (!WKM) return launch_glds<EPI, 64, 64, 2, 2, 8, false, false, false, 0, false, false, true>(args, stream, splits); break;      // (burst: the 4-wave 64x64 tile lost 3.5 % with the spread refill; r06: + PIPE, -6.1 %)
-    case 1566: if constexpr (!WKM) return launch_glds<EPI, 64, 64, 2, 2, 8, false>(args, stream, splits); break;      // the r03-r05 default (burst, plain loop)
-    case 1532: return launch_glds<EPI, 32, 128, 1, 4, 7, WKM>(args, stream, splits);
-    case 1900: return launch_glds<EPI, 192, 256, 2, 4, 2, WKM, false, false, 0, true, true, true>(args, stream, splits);      // (r06: + PIPE) r03: 3 tile rows for the SFT step's 560 rows (256-row tiles pad 27 %); r05: ASYM ring
-    case 1902: return launch_glds<EPI, 192, 256, 2, 4, 2, WKM, false, false, 0, true, true>(args, stream, splits);      // the r05 default (ASYM + spread, plain loop)
-    case 1901: return launch_glds<EPI, 192, 256, 2, 4, 2, WKM, false, true>(args, stream, splits);      // lab: the r03-r04 two-stage ring, refill requested first
-    // r05 lab (profiles/r05s_producer_waves.md; its driver left the tree in r06): the 128x128 ring with 4 producer waves (one per SIMD) issuing every LDS-DMA piece: bit-identical,
-    // 12-16 % SLOWER (piece issue is serial per wave: 4 waves x 12 pieces take longer than 8 x 6); the 128x256 / 192x256 tiles do not fit 12 waves' 168 registers.  Not used.
-    case 2100: return launch_glds<EPI, 128, 128, 2, 4, 4, WKM, false, GLDS_ISSUE_FIRST != 0, 4>(args, stream, splits);
-    case 1903: return launch_glds<EPI, 192, 256, 2, 4, 2, WKM, false, true, 0, true>(args, stream, splits);      // lab: ASYM with the refill requested first (41.9 us against 37.2)
-    case 1904: return launch_glds<EPI, 192, 256, 2, 4, 2, WKM, false, false, 0, true>(args, stream, splits);      // lab: asymmetric ring, refill as one burst
+    case 1506: return launch_glds<EPI, 64, 128, 2, 4, 6, WKM, false>(args, stream, splits);
+    case 1105: return launch_glds<EPI, 128, 128, 2, 4, 5, WKM, false>(args, stream, splits);
+    case 1564: if constexpr (!WKM) return launch_glds<EPI, 64, 64, 2, 2, 8, false, false, PIPE>(args, stream, splits); break;      // (burst: the 4-wave 64x64 tile lost 3.5 % with the spread refill; r06: + PIPE, -6.1 %)
+    case 1566: if constexpr (!WKM) return launch_glds<EPI, 64, 64, 2, 2, 8, false, false>(args, stream, splits); break;      // the r03-r05 default (burst, plain loop)
+    case 1532: return launch_glds<EPI, 32, 128, 1, 4, 7, WKM, false>(args, stream, splits);
+    case 1900: return launch_glds<EPI, 192, 256, 2, 4, 2, WKM, false, ASYM | SPREAD | PIPE>(args, stream, splits);      // (r06: + PIPE) r03: 3 tile rows for the SFT step's 560 rows (256-row tiles pad 27 %); r05: ASYM ring
+    case 1902: return launch_glds<EPI, 192, 256, 2, 4, 2, WKM, false, ASYM | SPREAD>(args, stream, splits);      // the r05 default (ASYM + spread, plain loop)
+    case 1901: return launch_glds<EPI, 192, 256, 2, 4, 2, WKM, false, IFIRST>(args, stream, splits);      // lab: the r03-r04 two-stage ring, refill requested first
+    case 1903: return launch_glds<EPI, 192, 256, 2, 4, 2, WKM, false, IFIRST | ASYM>(args, stream, splits);      // lab: ASYM with the refill requested first (41.9 us against 37.2)
+    case 1904: return launch_glds<EPI, 192, 256, 2, 4, 2, WKM, false, ASYM>(args, stream, splits);      // lab: asymmetric ring, refill as one burst
     default: break;
   }
-  if constexpr (WKM) {
-    vlaser_set_error("vlaser_gemm_nn: force_bm must be 0 or an LDS-DMA configuration code (got %d)", bm);
-    return -1;
+  if constexpr (!WKM) {                // the register-staged tiles
+    if (bm == 128) return launch_bm<EPI, 128>(args, stream, splits);
+    if (bm == 64) return launch_bm<EPI, 64>(args, stream, splits);
+    if (bm == 32) return launch_bm<EPI, 32>(args, stream, splits);
   }
-  if (bm == 128) return launch_bm<EPI, 128>(args, stream, splits);
-  if (bm == 64) return launch_bm<EPI, 64>(args, stream, splits);
-  return launch_bm<EPI, 32>(args, stream, splits);
+  vlaser_set_error("%s: force_bm = %d is not a configuration code of this form (see the table at force_bm in include/vlaser_hip.h)", WKM ? "vlaser_gemm_nn" : "vlaser_gemm", bm);
+  return -1;
 }
 
 // ---------------------------------------------------------------------------------------------- TN GEMM (weight gradients)
@@ -1460,9 +1363,6 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* lds_tile, int pitch, int c
   return u.b;
 }
 
-#ifndef TN_LOAD_LATE
-#define TN_LOAD_LATE 0
-#endif
 struct GemmTnP {
   const bf16_t* At; const bf16_t* Wt; bf16_t* out;
   int M, N, K, ldat, ldwt, ldo, tiles_m, tiles_n;
@@ -1483,12 +1383,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmTnP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave / WC, wc = wave % WC;
-  const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int tile_m = bid % p.tiles_m, tile_n = bid / p.tiles_m;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int tpg = (p.K + BK - 1) / BK, nk = tpg * p.groups;      // K-tiles per group run, total
@@ -1538,12 +1433,10 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmTnP p) {
     const int buf = kt & 1;
     const char* As = smem + buf * BUF;
     const char* Ws = As + 64 * PA;
-#if !TN_LOAD_LATE
     // (r03) tile kt+2 is requested at the TOP of the step: its register stage (nst ^ 1 held tile kt, which went to LDS before this step) is
     // already free, and the loads then fly under this step's 2 x (fragment reads + MFMAs) instead of starting behind the LDS store of kt+1
     load_tile(kt + 2, nst ^ 1);
     __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8 fa[MT], fw[NT];
@@ -1558,10 +1451,6 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmTnP p) {
     }
     store_tile(buf ^ 1, nst);
     __builtin_amdgcn_sched_barrier(0);
-#if TN_LOAD_LATE
-    load_tile(kt + 2, nst ^ 1);            // r02 order: the stage just consumed two steps ago, refilled behind the LDS store
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     __syncthreads();
   };
   // register stages alternate: tile kt+1 sits in stage (kt+1)&1; after it is stored, stage kt&1 (tile kt, already in LDS) is refilled with kt+2
@@ -1663,12 +1552,6 @@ extern "C" int vlaser_gemm_tn_lds(const void* At, const void* Wt, void* out, int
   return launch<VL_EPI_NONE, true, true>(&a, reinterpret_cast<hipStream_t>(s));
 }
 
-static bool glds_code(int bm) {      // every LDS-DMA configuration code launch<> knows (defaults + lab variants)
-  static const int codes[] = {1100, 1101, 1110, 1105, 1200, 1201, 1210, 1310, 1300, 1301, 1302, 1304, 1440, 1441, 1442, 1500, 1501, 1502, 1506, 1532, 1564, 1566, 1900, 1901, 1902, 1903, 1904, 2100};
-  for (int c : codes) if (c == bm) return true;
-  return false;
-}
-
 extern "C" int vlaser_gemm(int epi, const VlaserGemmArgs* a, vl_stream_t s) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(s);
   VL_CHECK(a && a->A && a->W, "vlaser_gemm: null operand");
@@ -1676,8 +1559,6 @@ extern "C" int vlaser_gemm(int epi, const VlaserGemmArgs* a, vl_stream_t s) {
   VL_CHECK(a->K % BK == 0, "vlaser_gemm: K=%d must be a multiple of %d", a->K, BK);
   VL_CHECK(a->batch <= 1 || (epi == VL_EPI_NONE || epi == VL_EPI_F32 || epi == VL_EPI_BIAS), "vlaser_gemm: batched mode supports NONE / F32 / BIAS epilogues");
   VL_CHECK(!a->sumsq_part, "vlaser_gemm: sumsq_part is honoured by vlaser_gemm_tn_lds only");
-  VL_CHECK(a->force_bm == 0 || a->force_bm == 32 || a->force_bm == 64 || a->force_bm == 128 || glds_code(a->force_bm),
-           "vlaser_gemm: force_bm must be 0/32/64/128 or an LDS-DMA configuration code 1100/1105/1200/1300/1301/1440/1500/1506/1532/1564/1900, 2100 (lab: producer waves)");
   VL_CHECK(a->lda % 8 == 0 && a->ldw % 8 == 0, "vlaser_gemm: lda/ldw must be multiples of 8 (16-byte rows)");
   VL_CHECK(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->W & 15) == 0, "vlaser_gemm: operands must be 16-byte aligned");
   // the row-major bf16 / fp32 output (and the residual read with its stride): rows must not overlap -- the epilogues bound their stores by N, not by ldo
@@ -1725,8 +1606,6 @@ extern "C" int vlaser_gemm_nn(int epi, const VlaserGemmArgs* a, vl_stream_t s) {
   VL_CHECK(a->M > 0 && a->N > 0 && a->K > 0 && a->K % BK == 0, "vlaser_gemm_nn: bad shape M=%d N=%d K=%d (K must be a multiple of %d)", a->M, a->N, a->K, BK);
   VL_CHECK(a->N % 8 == 0 && a->lda % 8 == 0 && a->ldw % 8 == 0 && a->ldw >= a->N, "vlaser_gemm_nn: N, lda, ldw must be multiples of 8 and ldw >= N");
   VL_CHECK(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->W & 15) == 0, "vlaser_gemm_nn: operands must be 16-byte aligned");
-  VL_CHECK(a->force_bm == 0 || (glds_code(a->force_bm) && a->force_bm != 1564 && a->force_bm != 1566),
-           "vlaser_gemm_nn: force_bm must be 0 or an LDS-DMA configuration code 1100/1105/1200/1300/1440/1500/1506/1532/1900, 2100 (lab: producer waves)");
   VL_CHECK(a->batch <= 1 || epi == VL_EPI_NONE || epi == VL_EPI_F32, "vlaser_gemm_nn: batched mode supports the NONE / F32 epilogues");
   VL_CHECK(!a->sumsq_part, "vlaser_gemm_nn: sumsq_part is honoured by vlaser_gemm_tn_lds only");
   switch (epi) {
