@@ -476,6 +476,18 @@ int vlaser_adamw(void* param_bf16, float* master, float* m, float* v, const void
  * max_norm > 0 (torch clip_grad_norm_; HF TrainingArguments.max_grad_norm) -- no host round trip between the norm and the update. */
 int vlaser_adamw_clipped(void* param_bf16, float* master, float* m, float* v, const void* grad_bf16, long long n, float lr, float beta1, float beta2,
                          float eps, float weight_decay, float grad_scale, const float* gnorm2, float max_norm, int step, vl_stream_t stream);
+/* AdamW with block-wise 8-bit moments -- the optimizer the reference's VLA trainer builds for both of its groups (bnb.optim.AdamW8bit,
+ * Vlaser_VLA/Simpler/src/agent/train.py:251-255,278-282).  A block = 128 consecutive elements; per block 128 uint8 codes + one fp32 absmax for each
+ * moment, moment = table[code] * absmax (table_m signed, table_v unsigned: float[256] ascending, ops.adamw8_codes()).  The fresh moments, the master
+ * update (from the FRESH fp32 moments), the bias correction, the decoupled decay and the clip factor are vlaser_adamw_clipped's; then absmax = max |x|
+ * over the block and code = the nearest table entry to x / absmax, except that a strictly positive second moment never takes code 0 (it takes 1).
+ * An all-zero block stores the zero codes and absmax 0.  slot (int32 per block, nullable together with m32 / v32 = every block 8-bit): -1 = 8-bit state,
+ * k >= 0 = fp32 moments at m32 / v32 [128 k, 128 k + 128), updated bit for bit as vlaser_adamw_clipped would.  n = a positive multiple of 128;
+ * param / grad / master / m32 / v32 16-byte aligned, the code arrays 8-byte.  gnorm2 NULL = no clipping. */
+int vlaser_adamw8_clipped(void* param_bf16, float* master, uint8_t* m_code, uint8_t* v_code, float* m_absmax, float* v_absmax, const int32_t* slot,
+                          float* m32, float* v32, const float* table_m, const float* table_v, const void* grad_bf16, long long n, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, float grad_scale, const float* gnorm2 /* NULL = no clipping */, float max_norm,
+                          int step, vl_stream_t stream);
 /* acc (fp32) = (first ? 0 : acc) + w * g (bf16); finalize: g = bf16(acc).  Gradient accumulation over micro-batches / the samples of a
  * per-device batch (…2nd_finetune_full.sh:5-6,49-50: PER_DEVICE_BATCH_SIZE, GRADIENT_ACC). */
 int vlaser_grad_accumulate(void* g_bf16, float* acc, long long n, float w, int first, int finalize, vl_stream_t stream);

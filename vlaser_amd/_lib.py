@@ -123,6 +123,7 @@ _SIGS = {
     'vlaser_sumsq_rows': [vp, vp, vp, i32, i32, i64, vp, i32, vp],
     'vlaser_sum_partials': [vp, i64, vp, i32, vp],
     'vlaser_adamw_clipped': [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, f32, i32, vp],
+    'vlaser_adamw8_clipped': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, f32, i32, vp],
     'vlaser_grad_accumulate': [vp, vp, i64, f32, i32, i32, vp],
     'vlaser_silu': [vp, vp, i64, vp],
     'vlaser_silu_bwd': [vp, vp, vp, i64, vp],

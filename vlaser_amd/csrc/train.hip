@@ -751,6 +751,154 @@ extern "C" int vlaser_adamw_clipped(void* p, float* master, float* m, float* v, 
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- AdamW with block-wise 8-bit moments
+// The reference's VLA trainer builds both of its optimizers as bnb.optim.AdamW8bit (Vlaser_VLA/Simpler/src/agent/train.py:251-255,278-282): exp_avg / exp_avg_sq
+// live as one uint8 code per element + one fp32 absmax per block, moment = table[code] * absmax (the "dynamic map" tables of ops.adamw8_codes()).  Here a
+// block is 128 consecutive elements of the flat shard.  Per block: dequantise, the fresh fp32 moments and the master update EXACTLY as adamw_kernel
+// forms them (the master is updated from the fresh moments, not from the re-quantised ones: the bitsandbytes order), then absmax over the block and the
+// nearest code of every element.  A block whose `slot` is k >= 0 keeps fp32 moments at m32 / v32 [128 k, 128 k + 128) (tensors below min_8bit_size).
+//
+// One element's update with the contraction pinned to what adamw_kernel's ISA does (hipcc, ROCm 7.2: v_pk_mul / v_pk_fma in its vector body):
+//   gr = g gscale;  m = fma(b1, m, c1 gr);  v = fma(b2, v, gr (c2 gr));  w = fma(decay, w, -(step (m / fma(rbc2, sqrt(v), eps))))
+// so that an fp32-slot block is bit-identical to vlaser_adamw_clipped on the same operands.
+struct Adamw8Consts { float b1, b2, c1, c2, eps, rbc2, step, decay, gscale; };
+__device__ __forceinline__ void adamw8_update(const Adamw8Consts& k, float g, float& m, float& v, float& w) {
+#pragma clang fp contract(off)
+  const float gr = g * k.gscale;
+  m = __builtin_fmaf(k.b1, m, k.c1 * gr);
+  v = __builtin_fmaf(k.b2, v, gr * (k.c2 * gr));
+  w = __builtin_fmaf(k.decay, w, -(k.step * (m / __builtin_fmaf(k.rbc2, sqrtf(v), k.eps))));
+}
+// max over the 16 lanes of a DPP row, the same bits in every lane (the butterfly of group16_sum)
+__device__ __forceinline__ float group16_max(float v) {
+  v = fmaxf(v, vl_dpp<0xB1>(v));
+  v = fmaxf(v, vl_dpp<0x4E>(v));
+  v = fmaxf(v, vl_dpp<0x141>(v));
+  v = fmaxf(v, vl_dpp<0x140>(v));
+  return v;
+}
+// index of the table value nearest to a (sorted ascending, 256 entries in LDS): 8 probes find the last entry <= a, one compare picks between it and its
+// successor.  Every index stays inside 0..255 whatever a is (NaN compares false: code 0).
+__device__ __forceinline__ uint32_t adamw8_nearest(const float* tab, float a) {
+  int pos = 0;
+#pragma unroll
+  for (int s = 128; s >= 1; s >>= 1) pos += tab[pos + s] <= a ? s : 0;
+  const int nx = pos < 255 ? pos + 1 : 255;
+  return (uint32_t)(tab[nx] - a < a - tab[pos] ? nx : pos);
+}
+// x / absmax without a division per element and without overflow for a denormal absmax: both are scaled by 2^64 (exact) below 2^-64
+__device__ __forceinline__ void adamw8_norm(float absmax, float& scale, float& rcp) {
+#pragma clang fp contract(off)
+  scale = absmax < 0x1p-64f ? 0x1p64f : 1.0f;
+  rcp = absmax > 0.f ? 1.0f / (absmax * scale) : 0.f;          // an all-zero block: every element normalises to 0, the zero code; no 0 / 0
+}
+// 16 lanes per block of 128 (8 elements a lane: one 16-byte gradient vector, two 16-byte master vectors, one 8-byte vector per code array), 4 blocks per
+// wave, 16 per workgroup.  Bytes per element: grad 2 + master 4 + 4 + codes 1 + 1 + 1 + 1 + param 2 = 16, + 4 x 4 B of absmax per 128 = 16.125 (fp32: 28).
+// Arithmetic per element besides adamw_kernel's: 2 LDS reads to dequantise + 2 x (8 + 2) to quantise = 22 ds_read_b32 and ~2 x 36 VALU operations
+// (probe: compare, select, add; the address folds into the read's offset).  At 5.5 TB/s the stream delivers 5.5e12 / 16.125 = 3.4e11 elements/s; the
+// 256 CUs issue 256 x 64 lanes x 2.4 GHz = 3.9e13 VALU lane-operations/s and 256 x 32 x 2.4e9 = 2.0e13 LDS reads/s (conflict-free) -- 115 operations and
+// 57 reads per element's time.  The search (~72 + adamw's ~45 with its division and square root) sits AT the VALU budget, not well under it: whether the
+// kernel keeps the bandwidth fraction of adamw_kernel is measured, not assumed (tools/micro/adamw8_lab.py, profiles/adamw8bit_ab.md).
+__global__ __launch_bounds__(256) void adamw8_kernel(bf16_t* __restrict__ p, float* __restrict__ master, uint8_t* __restrict__ m_code,
+                                                     uint8_t* __restrict__ v_code, float* __restrict__ m_absmax, float* __restrict__ v_absmax,
+                                                     const int32_t* __restrict__ slot, float* __restrict__ m32, float* __restrict__ v32,
+                                                     const float* __restrict__ table_m, const float* __restrict__ table_v, const bf16_t* __restrict__ g,
+                                                     long long n_blocks, float lr, float b1, float b2, float eps, float wd, float gscale, float bc1, float bc2,
+                                                     const float* __restrict__ gnorm2, float max_norm) {
+  __shared__ float tm[256], tv[256];
+  tm[threadIdx.x] = table_m[threadIdx.x];
+  tv[threadIdx.x] = table_v[threadIdx.x];
+  __syncthreads();
+  if (gnorm2) {          // adamw_kernel's clip factor, the same operations in the same order
+    const float gn = sqrtf(gnorm2[0]);
+    if (max_norm > 0.f && gn > max_norm) gscale *= max_norm / (gn + 1e-6f);
+  }
+  const Adamw8Consts k = {b1, b2, 1.0f - b1, 1.0f - b2, eps, rsqrtf(bc2), lr / bc1, __builtin_fmaf(-lr, wd, 1.0f), gscale};
+  const int lane = threadIdx.x & 15;
+  for (long long blk = (long long)blockIdx.x * 16 + (threadIdx.x >> 4); blk < n_blocks; blk += (long long)gridDim.x * 16) {
+    const long long e = blk * 128 + lane * 8;
+    const u32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(g + e));
+    const f32x4 wa = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(master + e)),
+                wb = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(master + e + 4));
+    const int sl = slot ? slot[blk] : -1;          // uniform over the 16 lanes of a block: the rows of a wave branch independently
+    float gr[8], m[8], v[8], w[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      gr[2 * j] = bf16lo_to_f32(gv[j]); gr[2 * j + 1] = bf16hi_to_f32(gv[j]);
+      w[j] = wa[j]; w[4 + j] = wb[j];
+    }
+    if (sl >= 0) {
+      float* mp = m32 + (long long)sl * 128 + lane * 8;
+      float* vp = v32 + (long long)sl * 128 + lane * 8;
+      const f32x4 ma = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(mp)), mb = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(mp + 4)),
+                  va = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(vp)), vb = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(vp + 4));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { m[j] = ma[j]; m[4 + j] = mb[j]; v[j] = va[j]; v[4 + j] = vb[j]; }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) adamw8_update(k, gr[j], m[j], v[j], w[j]);
+      __builtin_nontemporal_store(f32x4{m[0], m[1], m[2], m[3]}, reinterpret_cast<f32x4*>(mp));
+      __builtin_nontemporal_store(f32x4{m[4], m[5], m[6], m[7]}, reinterpret_cast<f32x4*>(mp + 4));
+      __builtin_nontemporal_store(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(vp));
+      __builtin_nontemporal_store(f32x4{v[4], v[5], v[6], v[7]}, reinterpret_cast<f32x4*>(vp + 4));
+    } else {
+      const u32x2 cm = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(m_code + e)),
+                  cv = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(v_code + e));
+      const float am0 = __builtin_nontemporal_load(m_absmax + blk), av0 = __builtin_nontemporal_load(v_absmax + blk);
+      float am1 = 0.f, av1 = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        m[j] = __fmul_rn(tm[(cm[j >> 2] >> (8 * (j & 3))) & 255u], am0);
+        v[j] = __fmul_rn(tv[(cv[j >> 2] >> (8 * (j & 3))) & 255u], av0);
+        adamw8_update(k, gr[j], m[j], v[j], w[j]);
+        am1 = fmaxf(am1, fabsf(m[j]));
+        av1 = fmaxf(av1, v[j]);
+      }
+      am1 = group16_max(am1);
+      av1 = group16_max(av1);
+      float sm, rm, sv, rv;
+      adamw8_norm(am1, sm, rm);
+      adamw8_norm(av1, sv, rv);
+      u32x2 qm = {0u, 0u}, qv = {0u, 0u};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const uint32_t c_m = adamw8_nearest(tm, __fmul_rn(__fmul_rn(m[j], sm), rm));
+        uint32_t c_v = adamw8_nearest(tv, __fmul_rn(__fmul_rn(v[j], sv), rv));
+        // a strictly positive second moment is never stored as 0: with gradient scales spread over decades inside a block, nearest rounding flushes the
+        // small ones and their next update divides by eps alone (80-190 x lr in an fp64 simulation; <= 1.4 x lr with the smallest positive code)
+        if (v[j] > 0.f && c_v == 0u) c_v = 1u;
+        qm[j >> 2] |= c_m << (8 * (j & 3));
+        qv[j >> 2] |= c_v << (8 * (j & 3));
+      }
+      __builtin_nontemporal_store(qm, reinterpret_cast<u32x2*>(m_code + e));
+      __builtin_nontemporal_store(qv, reinterpret_cast<u32x2*>(v_code + e));
+      if (lane == 0) {
+        __builtin_nontemporal_store(am1, m_absmax + blk);
+        __builtin_nontemporal_store(av1, v_absmax + blk);
+      }
+    }
+    __builtin_nontemporal_store(f32x4{w[0], w[1], w[2], w[3]}, reinterpret_cast<f32x4*>(master + e));
+    __builtin_nontemporal_store(f32x4{w[4], w[5], w[6], w[7]}, reinterpret_cast<f32x4*>(master + e + 4));
+    *reinterpret_cast<u32x4*>(p + e) = u32x4{pack_bf16x2(w[0], w[1]), pack_bf16x2(w[2], w[3]), pack_bf16x2(w[4], w[5]), pack_bf16x2(w[6], w[7])};      // default policy, as adamw_kernel
+  }
+}
+extern "C" int vlaser_adamw8_clipped(void* p, float* master, uint8_t* m_code, uint8_t* v_code, float* m_absmax, float* v_absmax, const int32_t* slot,
+                                     float* m32, float* v32, const float* table_m, const float* table_v, const void* g, long long n, float lr, float b1,
+                                     float b2, float eps, float wd, float gscale, const float* gnorm2, float max_norm, int step, vl_stream_t s) {
+  VL_CHECK(p && master && m_code && v_code && m_absmax && v_absmax && table_m && table_v && g && n > 0 && n % 128 == 0 && step >= 1,
+           "vlaser_adamw8_clipped: bad args (n = a positive multiple of the 128-element block)");
+  VL_CHECK((slot && m32 && v32) || (!slot && !m32 && !v32), "vlaser_adamw8_clipped: slot, m32 and v32 go together (all NULL = every block 8-bit)");
+  VL_CHECK((((uintptr_t)p | (uintptr_t)g | (uintptr_t)master | (uintptr_t)m32 | (uintptr_t)v32) & 15) == 0 && (((uintptr_t)m_code | (uintptr_t)v_code) & 7) == 0 &&
+           (((uintptr_t)m_absmax | (uintptr_t)v_absmax | (uintptr_t)slot | (uintptr_t)table_m | (uintptr_t)table_v) & 3) == 0, "vlaser_adamw8_clipped: alignment");
+  const float bc1 = 1.0f - powf(b1, (float)step), bc2 = 1.0f - powf(b2, (float)step);
+  const long long n_blocks = n / 128;
+  const int cap = adamw_grid_cap();
+  const int blocks = (int)((n_blocks + 15) / 16 < cap ? (n_blocks + 15) / 16 : cap);
+  hipLaunchKernelGGL(adamw8_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)s, (bf16_t*)p, master, m_code, v_code, m_absmax, v_absmax, slot, m32, v32,
+                     table_m, table_v, (const bf16_t*)g, n_blocks, lr, b1, b2, eps, wd, gscale, bc1, bc2, gnorm2, max_norm);
+  VL_LAUNCH_CHECK();
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------------- gradient accumulation
 // acc (fp32) = [acc +] w * g (bf16); with `finalize` the bf16 buffer is overwritten by the rounded sum -- micro-batches of a
 // gradient-accumulation step / samples of a per-device batch > 1 (the SFT launcher's PER_DEVICE_BATCH_SIZE x GRADIENT_ACC).

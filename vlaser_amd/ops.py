@@ -892,6 +892,52 @@ def adamw_clipped(param, master, m, v, grad, lr, beta1, beta2, eps, wd, gscale, 
                                          beta2, eps, wd, gscale, gnorm2.data_ptr(), max_norm or 0.0, step, _stream()), 'vlaser_adamw_clipped')
 
 
+_ADAMW8_CODES = None
+_ADAMW8_DEVICE_CODES = {}
+
+
+def adamw8_codes():
+    """(signed, unsigned): the two float32[256] code tables of the 8-bit AdamW moments, ascending -- bitsandbytes' "dynamic map" with 7 exponent bits
+    (its `create_dynamic_map(signed, 7, 8)`): decade i = 0..6 holds the midpoints of linspace(0.1, 1, 2^i + 1) (unsigned: 2^(i+1) + 1) times 10^(i-6),
+    plus 0 and 1; the signed table carries both signs.  Built in fp64, rounded to fp32 once (CPU tensors; `adamw8_clipped` keeps device copies)."""
+    global _ADAMW8_CODES
+    if _ADAMW8_CODES is None:
+        def table(signed):
+            vals = [0.0, 1.0]
+            for i in range(7):
+                n = 2 ** i if signed else 2 ** (i + 1)
+                b = [0.1 + j * (0.9 / n) for j in range(n + 1)]
+                b[-1] = 1.0
+                for j in range(n):
+                    x = (b[j] + b[j + 1]) / 2 * 10.0 ** (i - 6)
+                    vals += [x, -x] if signed else [x]
+            assert len(vals) == 256
+            return torch.tensor(sorted(vals), dtype=torch.float64).to(torch.float32)
+        _ADAMW8_CODES = (table(True), table(False))
+    return _ADAMW8_CODES
+
+
+def _adamw8_device_codes(device):
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    if key not in _ADAMW8_DEVICE_CODES:
+        _ADAMW8_DEVICE_CODES[key] = tuple(t.to(device) for t in adamw8_codes())
+    return _ADAMW8_DEVICE_CODES[key]
+
+
+def adamw8_dequant(code, absmax, table):
+    """The stored moment table[code] * absmax (one fp32 product per element, as the kernel forms it): code uint8 [n], absmax fp32 [n / 128].  Checkpoint
+    inspection, tests, debugging -- not on the hot path."""
+    return table.to(code.device)[code.long()] * absmax.repeat_interleave(128)
+
+
+def adamw8_clipped(param, master, m_code, v_code, m_absmax, v_absmax, slot, m32, v32, grad, lr, beta1, beta2, eps, wd, gscale, gnorm2, max_norm, step):
+    """AdamW with block-wise 8-bit moments (csrc/train.hip `adamw8_kernel`); slot / m32 / v32 None together = every block 8-bit; gnorm2 None = no clipping."""
+    tm, tv = _adamw8_device_codes(param.device)
+    L.check(L.lib().vlaser_adamw8_clipped(param.data_ptr(), master.data_ptr(), m_code.data_ptr(), v_code.data_ptr(), m_absmax.data_ptr(), v_absmax.data_ptr(),
+                                          _p(slot), _p(m32), _p(v32), tm.data_ptr(), tv.data_ptr(), grad.data_ptr(), param.numel(), lr, beta1, beta2, eps, wd,
+                                          gscale, _p(gnorm2), max_norm or 0.0, step, _stream()), 'vlaser_adamw8_clipped')
+
+
 def grad_accumulate(g, acc, w, first, finalize):
     L.check(L.lib().vlaser_grad_accumulate(g.data_ptr(), acc.data_ptr(), g.numel(), w, int(first), int(finalize), _stream()), 'vlaser_grad_accumulate')
 

@@ -28,7 +28,7 @@ from . import _lib as L
 from . import backward, ops
 from .config import VlaserConfig
 from .engine import BF, KVCache, VitEngine
-from .param_group import FlatParams, ParamGroup, behind_current, cut_buckets, decoder_layer_specs, mlp1_specs, pack_decoder_layer, pack_mlp1, unpack_decoder_layer, unpack_mlp1
+from .param_group import FlatParams, ParamGroup, behind_current, check_optimizer, cut_buckets, decoder_layer_specs, mlp1_specs, pack_decoder_layer, pack_mlp1, unpack_decoder_layer, unpack_mlp1
 
 F32 = torch.float32
 
@@ -128,8 +128,10 @@ class SFTModel(ParamGroup):
 
     def __init__(self, cfg: VlaserConfig, device='cuda', max_seq_len=576, max_tiles=1, lr=2e-5, weight_decay=0.05, betas=(0.9, 0.999),
                  eps=1e-8, max_grad_norm=1.0, process_group=None, bucket_layers=4, seed_state_dict=None, recompute=False, attn_bwd_block=1024, attn_bwd='fused',
-                 batch_rows=False, max_batch_tokens=None):
+                 batch_rows=False, max_batch_tokens=None, optimizer='adamw'):
         L.lib()
+        # 'adamw': fp32 moments; 'adamw8bit': block-wise 8-bit moments, as the reference's VLA trainer runs (param_group.py, csrc/train.hip `adamw8_kernel`)
+        self.optimizer = check_optimizer(optimizer)
         if not torch.cuda.is_available():
             raise L.VlaserHipError('vlaser_amd needs an MI355X (gfx950) GPU: there is no CPU fallback')
         self.cfg, self.device = cfg, torch.device(device)
@@ -198,7 +200,7 @@ class SFTModel(ParamGroup):
         for i in range(llm.num_hidden_layers):
             pack_decoder_layer(sd, f'language_model.model.layers.{i}.', fp.view, f'l{i}.', llm.head_dim)
         pack_mlp1(sd, fp.view)
-        self.init_group(fp, [hi for _, hi in buckets], self.world, self.rank)
+        self.init_group(fp, [hi for _, hi in buckets], self.world, self.rank, self.optimizer)
         # layer buckets hold the layers in reverse order, `bucket_layers` each (bucket 0 = lm_head + final norm, bucket 1 = the last layers)
         self.bucket_of_layer = {li: 1 + (llm.num_hidden_layers - 1 - li) // self.bucket_layers for li in range(llm.num_hidden_layers)}
         self._alloc_workspace()
@@ -1048,7 +1050,7 @@ class SFTModel(ParamGroup):
         if self.rank == 0:
             self.save_pretrained(path)
         self.wait_optimizer()
-        torch.save({'step_count': self.step_count, 'world': self.world, 'rank': self.rank, 'lr': self.lr, 'betas': self.betas, 'eps': self.eps,
+        torch.save({'step_count': self.step_count, 'world': self.world, 'rank': self.rank, 'lr': self.lr, 'betas': self.betas, 'optimizer': self.optimizer, 'eps': self.eps,
                     'weight_decay': self.wd, **self.optimizer_state()}, os.path.join(path, f'optimizer_rank{self.rank:05d}_of_{self.world:05d}.pt'))
 
     def load_checkpoint(self, path):

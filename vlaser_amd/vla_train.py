@@ -13,7 +13,7 @@ Mirrors the step semantics of the reference's VLA trainer without its control pl
                 the loss and the trained gradients depend on;
   * step      = gradient accumulation (`no_sync`, train.py:470-482), `clip_grad_norm_` (:504-507), AdamW per group with
                 `CosineAnnealingWarmupRestarts` (optim.py:31-160), DDP-mean gradients (here: the ZeRO-1 bucketed reduce-scatter /
-                all-gather of vlaser_amd/dp.py).  The reference uses bitsandbytes' 8-bit AdamW; this build keeps fp32 moments.
+                all-gather of vlaser_amd/dp.py).  The reference uses bitsandbytes' 8-bit AdamW: `optimizer='adamw8bit'`; the default keeps fp32 moments.
 
 The 5 expert rows (proprio + 4 action tokens) go through the MFMA GEMM kernels with every intermediate saved; their backward reuses
 the SFT kernels (dgrad on resident W^T, TN wgrad, RMSNorm / SwiGLU / RoPE backward) plus `vlaser_attn_rows_bwd` for the joint
@@ -30,7 +30,7 @@ from . import ops, prep
 from .config import VLAConfig
 from .engine import BF, KVCache, PrefillBuffers, QwenStack, VitEngine, prefill_begin, prefill_layer
 from .pizero import canonicalize_vla_state_dict, stage_pixels
-from .param_group import FlatParams, ParamGroup, decoder_layer_specs, pack_decoder_layer, unpack_decoder_layer
+from .param_group import FlatParams, ParamGroup, check_optimizer, decoder_layer_specs, pack_decoder_layer, unpack_decoder_layer
 
 F32 = torch.float32
 
@@ -124,8 +124,10 @@ class VLATrainer(ParamGroup):
     """`step(batch...)` = one optimizer update of the action expert on flow-matching samples (per-device batch B >= 1, sample by sample)."""
 
     def __init__(self, cfg: VLAConfig, device='cuda', lr=5e-5, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
-                 process_group=None, bucket_layers=8, train_vlm=False, vlm_lr=5e-5, vlm_weight_decay=0.0):
+                 process_group=None, bucket_layers=8, train_vlm=False, vlm_lr=5e-5, vlm_weight_decay=0.0, optimizer='adamw'):
         L.lib()
+        # 'adamw8bit': both groups keep block-wise 8-bit moments, as the reference builds both of its optimizers (bnb.optim.AdamW8bit, train.py:251-255,278-282)
+        self.optimizer = check_optimizer(optimizer)
         if not torch.cuda.is_available():
             raise L.VlaserHipError('vlaser_amd needs an MI355X (gfx950) GPU: there is no CPU fallback')
         self.cfg, self.device = cfg, torch.device(device)
@@ -174,7 +176,7 @@ class VLATrainer(ParamGroup):
             pack_decoder_layer(sd, f'action_expert.model.layers.{i}.', v, f'l{i}.', ex.head_dim)
         for nm, k in [('ae1', 'action_encoder.linear_1'), ('ae2', 'action_encoder.linear_2'), ('ae3', 'action_encoder.linear_3'), ('pe', 'proprio_encoder')]:
             v[nm + '.w'].copy_(g(k + '.weight')); v[nm + '.b'].copy_(g(k + '.bias'))
-        self.init_group(fp, bounds + [fp.n], self.world, self.rank)
+        self.init_group(fp, bounds + [fp.n], self.world, self.rank, self.optimizer)
         self.bucket_of_layer = {i: min(j // self.bucket_layers, len(self.buckets) - 2) for j, i in enumerate(reversed(range(Lyr)))}
         self._alloc()
         self._refresh_transposes()
@@ -496,7 +498,7 @@ class VLATrainer(ParamGroup):
             # moments of the ZeRO-1 shard -- not torch.optim state dicts)
             extra = {'action_optimizer': None, 'vlm_optimizer': None, 'action_lr_scheduler': None, 'vlm_lr_scheduler': None, 'wandb_id': None, 'n_averaged': 1}
             save_vla_checkpoint(path, sd, cnt_update=self.step_count, cnt_batch=cnt_batch, extra=extra)
-        st = {'rank': self.rank, 'world': self.world, 'step_count': self.step_count}
+        st = {'rank': self.rank, 'world': self.world, 'step_count': self.step_count, 'optimizer': self.optimizer}
         for g, prefix in zip(self.groups(), ('', 'vlm_')):      # 'vlm_': the VLM group's shard of the second optimiser (train_vlm)
             st.update(g.optimizer_state(prefix))
         torch.save(st, self._opt_shard_path(path))

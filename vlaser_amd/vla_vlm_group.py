@@ -79,7 +79,7 @@ class VLMGroup(ParamGroup):
         v['emb.pe.b'].copy_(vit.b_pe); vit.b_pe = v['emb.pe.b']
         v['emb.cls'].copy_(vit.cls); vit.cls = v['emb.cls']
         v['emb.pos'].copy_(vit.pos); vit.pos = v['emb.pos']
-        self.init_group(fp, bounds + [fp.n], world, tr.rank)
+        self.init_group(fp, bounds + [fp.n], world, tr.rank, tr.optimizer)
         self._alloc()
 
     def _alloc(self):
