@@ -214,7 +214,7 @@ typedef struct {
   const void* W;          /* bf16, FRAGMENT-MAJOR packed [k_splits][N/(16 T)][8 waves][K/(k_splits*256)][T tiles][64][8], T = tiles_per_unit (ops.pack_skinny) */
   int M, N, K, ldw;       /* N = padded row count (multiple of 32); ldw unused */
   int n_valid;            /* un-padded N (0 = N): logits / partial row length */
-  int tiles_per_unit;     /* 0/2: units of 32 rows; 6: units of 96 rows; 1: units of 16 rows (split-K partial outputs only); packing must match */
+  int tiles_per_unit;     /* 0/2: units of 32 rows; 1: units of 16 rows; packing must match */
   int k_splits;           /* grid.y; K % (k_splits*256) == 0 */
   float* out_f32;
   void* out; int ldo;
@@ -234,8 +234,8 @@ int vlaser_skinny(int prologue, int epi, const VlaserSkinnyArgs* args, vl_stream
  * action mixture active (10 Euler steps x 28 layers), HF Qwen2DecoderLayer under greedy decode -- with every shape a compile-time parameter, every load of a launch
  * issued in one straight-line block, and the down projection publishing the next layer's residual stream ONCE (bf16) instead of fp32 split-K slabs that every
  * consumer workgroup re-reduces.  All three take device pointers, are asynchronous on `stream`, return 0 / negative like everything else here.
- *   vlaser_chain_qkv : args as vlaser_skinny(VL_PRO_NORM, VL_SK_QKV_ROPE) with tiles_per_unit = 1, n_partials = 0 (x = the published residual stream) or 2 (see vlaser_chain_down2): one wave per 16-row
- *                      unit, RMSNorm + q/k/v GEMV + bias + RoPE + KV-cache scatter;  hidden 768 / 1536
+ *   vlaser_chain_qkv : args as vlaser_skinny(VL_PRO_NORM, VL_SK_QKV_ROPE) with tiles_per_unit = 1, n_partials = 0 (x = the published residual stream): one wave per 16-row
+ *                      unit (two at hidden 1536, one K half each), RMSNorm + q/k/v GEMV + bias + RoPE + KV-cache scatter;  hidden 768 / 1536
  *   vlaser_chain_gu  : args as vlaser_skinny(VL_PRO_NORM, VL_SK_SWIGLU) with tiles_per_unit = 2 (or 1: 16-row lane-local units) and 2 or 3 producer slabs: bit-identical outputs, all units of a workgroup
  *                      requested up front; h_out (nullable) = bf16(x + sum partials), the residual vlaser_chain_down adds back
  *   vlaser_chain_down: h_out [M, N] = bf16(res + x [M, K] @ W^T), W = down_proj.weight packed by ops.pack_down4 ([workgroup][7 waves][10 loads][groups][16 blocks][cols][8]):
@@ -257,14 +257,9 @@ int vlaser_chain_down_geometry(int N, int* cols, int* groups);      /* returns t
 int vlaser_chain_qkv(const VlaserSkinnyArgs* args, vl_stream_t stream);
 int vlaser_chain_gu(const VlaserSkinnyArgs* args, vl_stream_t stream);
 int vlaser_chain_down(const void* x, int ldx, const void* W, const void* res, void* h_out, int M, int N, int K, unsigned long long* dbg, vl_stream_t stream);
-/*   vlaser_chain_down2: the same contraction as two K halves on 256 workgroups of six columns (grid.y = half): out_f32 [2][M][N] fp32 slabs, no residual, no rounding;
- *                      W = ops.pack_down4(W, k_splits=2).  The consumer is vlaser_chain_qkv with n_partials = 2 (h = bf16(x + slab 0 + slab 1), stored to h_out by unit 0's
- *                      wave for the o_proj -> gate/up seam): half the activation bytes per CU of vlaser_chain_down, 24 more L2 loads per lane in the q/k/v launch */
-int vlaser_chain_down2_supported(int M, int N, int K);
-int vlaser_chain_qkv2_supported(int M, int N, int K);
-/* tools / tests: 1 = the one-wave-per-unit kernel of vlaser_chain_qkv at hidden 1536 too (default 0: two waves there, one K half each); returns the previous value */
-int vlaser_chain_qkv_set_waves(int n);
-int vlaser_chain_down2(const void* x, int ldx, const void* W, float* out_f32, int M, int N, int K, unsigned long long* dbg, vl_stream_t stream);
+/* (ABI 8: four entry points left without a change of number, no struct and no remaining prototype changed: vlaser_chain_down2, vlaser_chain_down2_supported,
+ * vlaser_chain_qkv2_supported -- the down projection as two K halves leaving fp32 slabs for q/k/v to fold, measured equal inside the chunk and never shipped --
+ * and vlaser_chain_qkv_set_waves, a process-global switch that only that comparison needed.  profiles/HISTORY.md keeps the measurement.) */
 
 /* (The two fused layer-step launches measured in r03 / r04 -- o_proj -> gate/up with an in-launch hand-off, +2.0 us in-chain; attention + o_proj in one launch,
  * break-even -- lost to the chain kernels above and left the library in r05 together with include/vlaser_hip_experimental.h: profiles/r03c_euler_fusion.md,

@@ -515,20 +515,6 @@ def test_chain_qkv_vs_skinny_and_fp32(ops, B, tok, H):
     assert float((kc[:, :, :385].float() - 3).abs().max()) == 0 and float((vtc[:, :, :, 385 + tok:].float() - 3).abs().max()) == 0
     for a_, b_ in zip(outs[0], outs[1]):           # vs the 8-wave kernel: the same values up to the fp32 summation order
         assert (a_.float() - b_.float()).abs().max().item() <= 2 ** -6 * max(1.0, b_.float().abs().max().item())
-    if H == 1536:          # hidden 1536 runs two waves per unit (one K half each) by default; the one-wave kernel stays reachable and agrees to the summation order
-        prev = L.lib().vlaser_chain_qkv_set_waves(1)
-        try:
-            assert prev == 0
-            q1 = torch.zeros(M, nq * 128, dtype=BF, device='cuda')
-            kc1 = torch.full((B, nkv, smax, 128), 3.0, dtype=BF, device='cuda'); vtc1 = torch.full((B, nkv, 128, smax), 3.0, dtype=BF, device='cuda')
-            a, keep = ops.skinny_args(h, pw, M, n_partials=0, norm_w=nw, bias=B16, q_out=q1, k_cache=kc1, vt_cache=vtc1, rope_cos=cos, rope_sin=sin, pos_ids=pos,
-                                      n_q_heads=nq, n_kv_heads=nkv, s_max=smax, tok_per_batch=tok, slot_base=385)
-            ops.launch_chain_qkv(a)
-        finally:
-            L.lib().vlaser_chain_qkv_set_waves(prev)
-        close(q1.view(M, nq, 128), _rope_ref(q, pos), name='q, one wave per unit')
-        for a_, b_ in zip((q1, kc1, vtc1), outs[1]):
-            assert (a_.float() - b_.float()).abs().max().item() <= 2 ** -6 * max(1.0, b_.float().abs().max().item())
     # slot_base < 0: the cache slot is the row's position id (graph-replayable decode)
     kc2 = torch.zeros(B, nkv, smax, 128, dtype=BF, device='cuda'); vtc2 = torch.zeros(B, nkv, 128, smax, dtype=BF, device='cuda')
     pos2 = (torch.arange(tok).repeat(B) + 100).int().cuda()
@@ -567,61 +553,6 @@ def test_chain_down_vs_fp32(ops, M, N):
     ops.chain_down(xs, w4, res, out2, M, N, K)
     assert torch.equal(out2, first[:M])
     assert not ops.chain_down_supported(M, N, 18944) and not ops.chain_down_supported(17, N, K)
-
-
-@pytest.mark.parametrize('M,N', [(4, 768), (5, 768), (1, 1536), (4, 1536), (8, 768), (3, 776)])
-def test_chain_down2_and_qkv_slabs(ops, M, N):
-    """r05: the down projection as two K halves on six-column workgroups (vlaser_chain_down2: fp32 slabs, no residual) -- the slabs sum to x @ W^T, deterministic --
-    and its consumer: vlaser_chain_qkv with n_partials = 2 == the same launch on the pre-reduced stream h = bf16(res + slab 0 + slab 1) bit for bit, h stored by unit 0."""
-    from vlaser_amd import _lib as L
-    K = 8960
-    assert bool(L.lib().vlaser_chain_down2_supported(M, N, K))
-    x, w = rnd(M, K, std=0.7), rnd(N, K, std=0.03, seed=1)
-    w42 = ops.pack_down4(w, k_splits=2)
-    slabs = torch.full((2, M + 1, N), 9.0, device='cuda')[:, :M].contiguous()
-    side = torch.cuda.Stream(); junk = torch.randn(4096, 4096, device='cuda')
-    first = None
-    for rep in range(6):
-        out = torch.full((2 * M * N + 8,), 9.0, device='cuda')
-        with torch.cuda.stream(side):
-            junk @ junk
-        ops.chain_down2(x, w42, out, M, N, K)
-        first = out.clone() if first is None else first
-        assert torch.equal(out, first), rep
-    torch.cuda.synchronize()
-    assert float((first[2 * M * N:] - 9).abs().max()) == 0
-    sl = first[:2 * M * N].view(2, M, N)
-    ref = x.float() @ w.float().t()
-    close(sl.sum(0), ref, rtol=4e-3, atol=4e-3 * ref.abs().max().item(), name='sum of the two K halves')
-    close(sl[0], x[:, :K // 2].float() @ w[:, :K // 2].float().t(), rtol=4e-3, atol=4e-3 * ref.abs().max().item(), name='first half')
-    if N not in (768, 1536) or not bool(L.lib().vlaser_chain_qkv2_supported(M, 2048, N)):
-        return
-    # the consumer: q/k/v from (res, slabs) == q/k/v from h = bf16(res + s0 + s1)
-    H, nq, nkv, smax, tok = N, 12, 2, 448, M
-    res, nw = rnd(M, H, std=1.5, seed=2), (1 + 0.1 * rnd(H, seed=5).float()).to(BF)
-    h = (sl[0] + sl[1] + res.float()).to(BF)
-    W16, B16 = ops.pack_qkv16(rnd(nq * 128, H, std=0.03, seed=1), rnd(nkv * 128, H, std=0.03, seed=2), rnd(nkv * 128, H, std=0.03, seed=3), rnd(nq * 128, std=0.3, seed=4),
-                              rnd(nkv * 128, std=0.3, seed=5), rnd(nkv * 128, std=0.3, seed=6))
-    pw = ops.pack_skinny(W16, 1, 1)
-    cos, sin = ops.rope_table(64)
-    pos = (torch.arange(tok) + 2).int().cuda()
-    outs = []
-    from vlaser_amd import _lib as L
-    prev = L.lib().vlaser_chain_qkv_set_waves(1)       # the slab form runs one wave per unit: the bit-level comparison needs the plain form in the same summation order (hidden 1536 defaults to two)
-    try:
-        for x_in, parts, npart in ((h, None, 0), (res, sl.contiguous(), 2)):
-            q_out = torch.zeros(M, nq * 128, dtype=BF, device='cuda')
-            kc = torch.zeros(1, nkv, smax, 128, dtype=BF, device='cuda'); vtc = torch.zeros(1, nkv, 128, smax, dtype=BF, device='cuda')
-            hA = torch.full((M, H), 7.0, dtype=BF, device='cuda')
-            a, keep = ops.skinny_args(x_in, pw, M, partials=parts, n_partials=npart, norm_w=nw, h_out=hA, bias=B16, q_out=q_out, k_cache=kc, vt_cache=vtc, rope_cos=cos, rope_sin=sin,
-                                      pos_ids=pos, n_q_heads=nq, n_kv_heads=nkv, s_max=smax, tok_per_batch=tok, slot_base=385)
-            ops.launch_chain_qkv(a)
-            outs.append((q_out, kc, vtc, hA))
-    finally:
-        L.lib().vlaser_chain_qkv_set_waves(prev)
-    for a_, b_ in zip(outs[0][:3], outs[1][:3]):
-        assert torch.equal(a_, b_)
-    assert torch.equal(outs[1][3], h) and float((outs[0][3].float() - 7).abs().max()) == 0
 
 
 def test_norms(ops):

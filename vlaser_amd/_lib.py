@@ -76,10 +76,6 @@ _SIGS = {
     'vlaser_chain_oproj': [C.POINTER(SkinnyArgs), vp],
     'vlaser_chain_gu': [C.POINTER(SkinnyArgs), vp],
     'vlaser_chain_down': [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp],
-    'vlaser_chain_down2_supported': [i32, i32, i32],
-    'vlaser_chain_qkv2_supported': [i32, i32, i32],
-    'vlaser_chain_qkv_set_waves': [i32],
-    'vlaser_chain_down2': [vp, i32, vp, vp, i32, i32, i32, vp, vp],
     'vlaser_layernorm': [vp, vp, vp, vp, i32, i32, f32, vp],
     'vlaser_rmsnorm': [vp, vp, vp, i32, i32, f32, vp],
     'vlaser_im2col': [vp, vp, i32, i32, i32, vp],

@@ -264,7 +264,8 @@ extern "C" int vlaser_chain_gu(const VlaserSkinnyArgs* a, vl_stream_t s) {
 
 // ------------------------------------------------------------------------------------------------------------------ q / k / v
 struct ChainQkvP {
-  const bf16_t* h_in; const float* partials; bf16_t* h_out; const bf16_t* norm_w; const u32x4* W; const bf16_t* bias;
+  const bf16_t* h_in; const float* partials; bf16_t* h_out; const bf16_t* norm_w; const u32x4* W; const bf16_t* bias;      // (partials, h_out: unread -- without them hipcc fetches the
+                                                                                                                          // arguments in other pieces and schedules the prologue differently)
   bf16_t* q_out; bf16_t* k_cache; bf16_t* vt_cache; const float* rope_cos; const float* rope_sin; const int32_t* pos_ids;
   int M, n_q_heads, n_kv_heads, s_max, tok_per_batch, slot_base;
   float eps;
@@ -273,15 +274,14 @@ struct ChainQkvP {
 
 // KS = K / 32 K-steps (24: hidden 768, 48: hidden 1536), RG = ceil(M / 4) row groups of the norm prologue.  One wave = one 16-row unit of the fused q/k/v
 // matrix (head_perm16 packing: lane group g of a unit holds [d, d+1, d+64, d+65], d = 8 (unit % 8) + 2 g -- the RoPE partner of every value in the same lane).
-// SP = 0: h_in is the residual stream itself; SP = 2: h = bf16(h_in + slab 0 + slab 1), the two K halves of vlaser_chain_down2 (slabs first, residual last: the
-// order of every other seam here), and unit 0's wave stores h for the o_proj -> gate/up seam.
+// h_in is the residual stream itself (already reduced and rounded: the action encoder's output, or what vlaser_chain_down published).
 // NWV = 2 (hidden 1536, the greedy decode): two waves per unit, each over one K half -- 24 weight requests and 24 dependent MFMAs per wave instead of 48 (6.6 -> 5.x us per
 // launch); both waves load the whole row (3 KB from L2) for the row's sum of squares and normalise their own half into their own LDS rows (still wave-local); wave 1 hands its
 // accumulator to wave 0 through LDS (the launch's only barrier).
-template <int KS, int RG, int SP, int NWV, bool DBG>
+template <int KS, int RG, int NWV, bool DBG>
 __global__ __launch_bounds__(64 * NWV) void chain_qkv_kernel(ChainQkvP p) {
   constexpr int K = KS * 32, NCH = KS / 4, KSW = KS / NWV, NCW = NCH / NWV, XS = (K / NWV) * 2 + 16;        // NCH: 16-byte chunks of a row per lane of its 16-lane group
-  static_assert(NWV == 1 || ((NWV == 2 || NWV == 4) && SP == 0 && KS % (4 * NWV) == 0), "several waves: plain residual stream, whole chunks per K part");
+  static_assert(NWV == 1 || ((NWV == 2 || NWV == 4) && KS % (4 * NWV) == 0), "several waves: whole chunks per K part");
   extern __shared__ __attribute__((aligned(16))) char smem_q[];    // [NWV][4 RG][XS] normalised activations (bf16) | NWV = 2: f32x4[64] of wave 1's accumulator
   const int lane = threadIdx.x & 63, wv = NWV == 1 ? 0 : (int)(threadIdx.x >> 6), fr = lane & 15, g = lane >> 4, r4 = lane >> 4, j16 = lane & 15;
   char* xs = smem_q + wv * (4 * RG * XS);
@@ -291,23 +291,13 @@ __global__ __launch_bounds__(64 * NWV) void chain_qkv_kernel(ChainQkvP p) {
   // ---- requests, in issue order: position id of the lane's row (cos / sin hang off it), norm weight + residual stream (L2), epilogue bias, weights (HBM)
   const int pos = p.pos_ids[min(fr, M - 1)];
   u32x4 wn[NCH], hc[RG][NCH];
-  f32x4 q[RG][NCH][SP > 0 ? 2 * SP : 1];
 #pragma unroll
   for (int i = 0; i < NCH; ++i) wn[i] = ld_global_16(p.norm_w + (j16 + 16 * i) * 8);
 #pragma unroll
   for (int rg = 0; rg < RG; ++rg) {
     const int row = min(rg * 4 + r4, M - 1);
 #pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int off = row * K + (j16 + 16 * i) * 8;
-      hc[rg][i] = ld_global_16(p.h_in + off);
-#pragma unroll
-      for (int u = 0; u < SP; ++u) {
-        const float* pp = p.partials + (off + u * (M * K));
-        q[rg][i][2 * u] = *reinterpret_cast<const f32x4*>(pp);
-        q[rg][i][2 * u + 1] = *reinterpret_cast<const f32x4*>(pp + 4);
-      }
-    }
+    for (int i = 0; i < NCH; ++i) hc[rg][i] = ld_global_16(p.h_in + (row * K + (j16 + 16 * i) * 8));
   }
   const u32x2 bias = *reinterpret_cast<const u32x2*>(p.bias + unit * 16 + g * 4);
   __builtin_amdgcn_sched_barrier(0);           // pin the issue order: vmcnt retires in order, the scheduler does not know
@@ -329,19 +319,6 @@ __global__ __launch_bounds__(64 * NWV) void chain_qkv_kernel(ChainQkvP p) {
   // ---- RMSNorm: xn = bf16(w * bf16(h * rsqrt(mean(h^2) + eps))), one row per 16-lane group and row group; wave-local (no barrier)
 #pragma unroll
   for (int rg = 0; rg < RG; ++rg) {
-    if constexpr (SP > 0) {
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) {
-        float sl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int u = 0; u < SP; ++u)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { sl[e] += q[rg][i][2 * u][e]; sl[4 + e] += q[rg][i][2 * u + 1][e]; }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hc[rg][i][e] = pack_bf16x2(sl[2 * e] + bf16lo_to_f32(hc[rg][i][e]), sl[2 * e + 1] + bf16hi_to_f32(hc[rg][i][e]));
-        if (blockIdx.x == 0 && rg * 4 + r4 < M) st_global_16(p.h_out + (size_t)(rg * 4 + r4) * K + (j16 + 16 * i) * 8, hc[rg][i]);
-      }
-    }
     float ssq = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i)
@@ -433,17 +410,12 @@ __global__ __launch_bounds__(64 * NWV) void chain_qkv_kernel(ChainQkvP p) {
 }
 
 extern "C" int vlaser_chain_qkv_supported(int M, int N, int K) { return M >= 1 && ((K == 768 && M <= 16) || (K == 1536 && M <= 8)) && N % 128 == 0; }      // (hidden 1536 x 16 rows would spill)
-static int g_qkv_waves = 0;            // tools / tests: 1 forces the one-wave kernel at hidden 1536 (same-box A/B, order-of-summation tests); 0 = the defaults below
-extern "C" int vlaser_chain_qkv_set_waves(int n) { const int prev = g_qkv_waves; if (n == 0 || n == 1) g_qkv_waves = n; return prev; }
-/* with the two fp32 slabs of vlaser_chain_down2 as input (n_partials = 2) */
-extern "C" int vlaser_chain_qkv2_supported(int M, int N, int K) { return M >= 1 && ((K == 768 && M <= 8) || (K == 1536 && M <= 4)) && N % 128 == 0; }
 
 extern "C" int vlaser_chain_qkv(const VlaserSkinnyArgs* a, vl_stream_t s) {
   VL_CHECK(a && a->x && a->W && a->norm_w && a->bias && a->q_out && a->k_cache && a->vt_cache && a->rope_cos && a->rope_sin && a->pos_ids, "vlaser_chain_qkv: null operand");
   VL_CHECK(a->tiles_per_unit == 1 && a->k_splits == 1, "vlaser_chain_qkv: weights packed in 16-row lane-local units (pack_qkv16 + pack_skinny(..., 1, 1))");
-  VL_CHECK(a->n_partials == 0 || (a->n_partials == 2 && a->partials && a->h_out), "vlaser_chain_qkv: reads the residual stream as published by vlaser_chain_down (no slabs) or x + the two slabs of vlaser_chain_down2 (then h_out receives the rounded sum)");
-  VL_CHECK(a->n_partials == 0 ? vlaser_chain_qkv_supported(a->M, a->N, a->K) : vlaser_chain_qkv2_supported(a->M, a->N, a->K),
-           "vlaser_chain_qkv: built for hidden 768 / 1536, M <= 16 (8 / 4 with slabs), whole heads (got M %d N %d K %d slabs %d)", a->M, a->N, a->K, a->n_partials);
+  VL_CHECK(a->n_partials == 0, "vlaser_chain_qkv: reads the residual stream as published by vlaser_chain_down (no slabs; got %d)", a->n_partials);
+  VL_CHECK(vlaser_chain_qkv_supported(a->M, a->N, a->K), "vlaser_chain_qkv: built for hidden 768 / 1536, M <= 16 (8 at 1536), whole heads (got M %d N %d K %d)", a->M, a->N, a->K);
   VL_CHECK(((uintptr_t)a->W & 15) == 0 && ((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->norm_w & 15) == 0 && ((uintptr_t)a->bias & 7) == 0, "vlaser_chain_qkv: alignment");
   ChainQkvP p;
   p.h_in = (const bf16_t*)a->x; p.partials = a->partials; p.h_out = (bf16_t*)a->h_out; p.norm_w = (const bf16_t*)a->norm_w; p.W = (const u32x4*)a->W; p.bias = (const bf16_t*)a->bias;
@@ -452,21 +424,19 @@ extern "C" int vlaser_chain_qkv(const VlaserSkinnyArgs* a, vl_stream_t s) {
   p.slot_base = a->slot_base; p.eps = a->eps; p.dbg = a->dbg;
   const int units = a->N / 16, rg = (a->M + 3) / 4, ks = a->K / 32;
   // waves per unit (K parts): hidden 1536 two (measured in the decode step: 0.9745 -> 0.9595 ms per token), hidden 768 one
-  const int nwv = (a->n_partials == 0 && ks == 48 && g_qkv_waves != 1) ? 2 : 1;
+  const int nwv = ks == 48 ? 2 : 1;
   const int lds = nwv * 4 * rg * (a->K / nwv * 2 + 16) + (nwv - 1) * 64 * 16;
   hipStream_t stream = (hipStream_t)s;
-#define CQ_LAUNCH(KS_, RG_, SP_, NWV_, DBG_)                                                                            \
+#define CQ_LAUNCH(KS_, RG_, NWV_, DBG_)                                                                                 \
   do {                                                                                                                  \
-    if (int rc = set_max_lds_once(chain_qkv_kernel<KS_, RG_, SP_, NWV_, DBG_>, lds)) return rc;                          \
-    hipLaunchKernelGGL((chain_qkv_kernel<KS_, RG_, SP_, NWV_, DBG_>), dim3(units), dim3(64 * NWV_), lds, stream, p);     \
+    if (int rc = set_max_lds_once(chain_qkv_kernel<KS_, RG_, NWV_, DBG_>, lds)) return rc;                               \
+    hipLaunchKernelGGL((chain_qkv_kernel<KS_, RG_, NWV_, DBG_>), dim3(units), dim3(64 * NWV_), lds, stream, p);          \
     VL_LAUNCH_CHECK();                                                                                                  \
     return 0;                                                                                                           \
   } while (0)
-#define CQ_CASEW(KS_, RG_, SP_, NWV_) if (ks == KS_ && rg == RG_ && a->n_partials == SP_ && nwv == NWV_) { if (p.dbg) CQ_LAUNCH(KS_, RG_, SP_, NWV_, true); else CQ_LAUNCH(KS_, RG_, SP_, NWV_, false); }
-#define CQ_CASE(KS_, RG_, SP_) CQ_CASEW(KS_, RG_, SP_, 1)
-  CQ_CASE(24, 1, 0) CQ_CASE(24, 2, 0) CQ_CASE(24, 3, 0) CQ_CASE(24, 4, 0) CQ_CASE(48, 1, 0) CQ_CASE(48, 2, 0) CQ_CASE(24, 1, 2) CQ_CASE(24, 2, 2) CQ_CASE(48, 1, 2)
-  CQ_CASEW(48, 1, 0, 2) CQ_CASEW(48, 2, 0, 2)      // (measured and not kept: four waves at hidden 1536 0.9709 vs 0.9697 ms per token; two waves at hidden 768 11.656 vs 11.645 ms per chunk)
-#undef CQ_CASEW
+#define CQ_CASE(KS_, RG_, NWV_) if (ks == KS_ && rg == RG_ && nwv == NWV_) { if (p.dbg) CQ_LAUNCH(KS_, RG_, NWV_, true); else CQ_LAUNCH(KS_, RG_, NWV_, false); }
+  CQ_CASE(24, 1, 1) CQ_CASE(24, 2, 1) CQ_CASE(24, 3, 1) CQ_CASE(24, 4, 1)
+  CQ_CASE(48, 1, 2) CQ_CASE(48, 2, 2)      // (measured and not kept: four waves at hidden 1536 0.9709 vs 0.9697 ms per token; two waves at hidden 768 11.656 vs 11.645 ms per chunk)
 #undef CQ_CASE
 #undef CQ_LAUNCH
   vlaser_set_error("vlaser_chain_qkv: no variant");
@@ -475,7 +445,7 @@ extern "C" int vlaser_chain_qkv(const VlaserSkinnyArgs* a, vl_stream_t s) {
 
 // ------------------------------------------------------------------------------------------------------------------ down projection
 struct ChainDownP {
-  const bf16_t* x; const u32x4* W; const bf16_t* res; bf16_t* h_out; float* out_f32;
+  const bf16_t* x; const u32x4* W; const bf16_t* res; bf16_t* h_out; float* out_f32;      // (out_f32: unread, kept so that the kernel arguments stay where the measured kernels fetch them)
   int M, N, ldx;
   unsigned long long* dbg;
 };
@@ -488,35 +458,29 @@ struct ChainDownP {
 // COLS = 3 puts N = 768 on 256 workgroups: a CU sustains ~35 GB/s of requests, so the launch lasts as long as the bytes of its busiest CU -- 54 KB of weights + the
 // whole [M, K] activation (every workgroup contracts over all of K: the price of publishing the result once) instead of 72 + 71 KB on 192 CUs.
 // RG = ceil(M / 4) row groups.
-// KS = 2 (vlaser_chain_down2, grid.y = K half): every byte a CU pulls costs the same ~17 ns / KB whether it comes from HBM or from L2 (r05d timeline: 71 -> 125 ->
-// 143 KB per CU = 2.7 -> 3.75 -> 3.95 us), and at KS = 1 more than half of a CU's bytes are the activation.  Two K halves x 128 six-column workgroups = 256
-// workgroups of 54 KB weights + HALF the activation; the halves leave two fp32 slabs [2][M][N] that the q/k/v launch (one wave per unit: 24 more L2 loads per lane,
-// inside the shadow of its weight round trip) and the next gate/up's residual path reduce -- no bf16 rounding here, the consumer rounds h = bf16(res + s0 + s1).
-template <int NW, int NL, int RG, int COLS, int CG, int KS, bool DBG>
+template <int NW, int NL, int RG, int COLS, int CG, bool DBG>
 __global__ __launch_bounds__(NW * 64) void chain_down_kernel(ChainDownP p) {
   __shared__ __attribute__((aligned(16))) float part[NW][CG][RG][4][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = lane >> 2, i = lane & 3;
-  const int M = p.M, n0 = blockIdx.x * (COLS * CG), kh = KS > 1 ? blockIdx.y : 0;
-  unsigned long long* dbg = DBG ? p.dbg + ((size_t)kh * gridDim.x + blockIdx.x) * 8 : nullptr;
+  const int M = p.M, n0 = blockIdx.x * (COLS * CG);
+  unsigned long long* dbg = DBG ? p.dbg + (size_t)blockIdx.x * 8 : nullptr;
   CH_STAMP(0);
   // ---- requests: residual (final phase: thread t -> row t / CG... see below), activations (L2), weights (HBM)
   const int fr_row = min(tid / CG, M - 1), fr_cg = tid % CG;            // final phase: thread t < M * CG finishes row t / CG of column group t % CG
   float rres[COLS];
-  if constexpr (KS == 1) {
-    const bf16_t* rp = p.res + (size_t)fr_row * p.N + n0 + fr_cg * COLS;
+  const bf16_t* rp = p.res + (size_t)fr_row * p.N + n0 + fr_cg * COLS;
 #pragma unroll
-    for (int c = 0; c < COLS; ++c) rres[c] = bf16_to_f32(rp[c]);          // unconditional (clamped): no branch in front of the load burst
-  }
+  for (int c = 0; c < COLS; ++c) rres[c] = bf16_to_f32(rp[c]);          // unconditional (clamped): no branch in front of the load burst
   u32x4 xv[RG][NL], wv[CG][NL];
 #pragma unroll
   for (int rg = 0; rg < RG; ++rg) {
-    const bf16_t* xr = p.x + (size_t)min(rg * 4 + i, M - 1) * p.ldx + ((kh * NW + wave) * NL) * 128 + b * 8;
+    const bf16_t* xr = p.x + (size_t)min(rg * 4 + i, M - 1) * p.ldx + (wave * NL) * 128 + b * 8;
 #pragma unroll
     for (int l = 0; l < NL; ++l) xv[rg][l] = ld_global_16(xr + l * 128);
   }
   __builtin_amdgcn_sched_barrier(0);           // activations (L2) strictly in front of the weights (HBM) in the queue
   {
-    const u32x4* src = p.W + ((((size_t)kh * gridDim.x + blockIdx.x) * NW + wave) * NL) * (CG * 16 * COLS) + b * COLS + min(i, COLS - 1);
+    const u32x4* src = p.W + (((size_t)blockIdx.x * NW + wave) * NL) * (CG * 16 * COLS) + b * COLS + min(i, COLS - 1);
 #pragma unroll
     for (int l = 0; l < NL; ++l)
 #pragma unroll
@@ -563,15 +527,9 @@ __global__ __launch_bounds__(NW * 64) void chain_down_kernel(ChainDownP p) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) s4[r] += t[r];
     }
-    if constexpr (KS == 1) {
-      bf16_t* op = p.h_out + (size_t)fr_row * p.N + n0 + fr_cg * COLS;
+    bf16_t* op = p.h_out + (size_t)fr_row * p.N + n0 + fr_cg * COLS;
 #pragma unroll
-      for (int c = 0; c < COLS; ++c) op[c] = f32_to_bf16(s4[c] + rres[c]);
-    } else {
-      float* op = p.out_f32 + ((size_t)kh * M + fr_row) * p.N + n0 + fr_cg * COLS;
-#pragma unroll
-      for (int c = 0; c < COLS; ++c) op[c] = s4[c];
-    }
+    for (int c = 0; c < COLS; ++c) op[c] = f32_to_bf16(s4[c] + rres[c]);
   }
   CH_STAMP(5);
 }
@@ -605,8 +563,8 @@ extern "C" int vlaser_chain_down(const void* x, int ldx, const void* W, const vo
   hipStream_t stream = (hipStream_t)s;
 #define CD_LAUNCH(RG_, COLS_, CG_)                                                                                                       \
   do {                                                                                                                                   \
-    if (dbg) hipLaunchKernelGGL((chain_down_kernel<7, 10, RG_, COLS_, CG_, 1, true>), dim3(wgs), dim3(7 * 64), 0, stream, p);              \
-    else hipLaunchKernelGGL((chain_down_kernel<7, 10, RG_, COLS_, CG_, 1, false>), dim3(wgs), dim3(7 * 64), 0, stream, p);                 \
+    if (dbg) hipLaunchKernelGGL((chain_down_kernel<7, 10, RG_, COLS_, CG_, true>), dim3(wgs), dim3(7 * 64), 0, stream, p);                 \
+    else hipLaunchKernelGGL((chain_down_kernel<7, 10, RG_, COLS_, CG_, false>), dim3(wgs), dim3(7 * 64), 0, stream, p);                    \
     VL_LAUNCH_CHECK();                                                                                                                   \
     return 0;                                                                                                                            \
   } while (0)
@@ -617,31 +575,6 @@ extern "C" int vlaser_chain_down(const void* x, int ldx, const void* W, const vo
 #undef CD_CASE2
 #undef CD_LAUNCH
   vlaser_set_error("vlaser_chain_down: no variant");
-  return -1;
-}
-
-/* The same contraction split into two K halves (grid.y): out_f32 [2][M][N] fp32 slabs, no residual, no rounding.  W = ops.pack_down4(W, k_splits=2):
- * [K half][workgroup][7 waves][5 loads][2 groups][16 blocks][cols][8]; a workgroup owns 2 x cols output columns (cols = 3 when N % 6 == 0, else 4 with N % 8 == 0). */
-extern "C" int vlaser_chain_down2_supported(int M, int N, int K) { return M >= 1 && M <= 8 && K == 8960 && (N % 6 == 0 || N % 8 == 0); }
-extern "C" int vlaser_chain_down2(const void* x, int ldx, const void* W, float* out_f32, int M, int N, int K, unsigned long long* dbg, vl_stream_t s) {
-  VL_CHECK(x && W && out_f32, "vlaser_chain_down2: null operand");
-  VL_CHECK(vlaser_chain_down2_supported(M, N, K) && ldx >= K && ldx % 8 == 0, "vlaser_chain_down2: built for K = 8960 (2 halves x 7 waves x 5 loads x 128), N %% 6 == 0 or N %% 8 == 0, M <= 8 (got M %d N %d K %d)", M, N, K);
-  VL_CHECK(((uintptr_t)W & 15) == 0 && ((uintptr_t)x & 15) == 0, "vlaser_chain_down2: alignment");
-  ChainDownP p;
-  p.x = (const bf16_t*)x; p.W = (const u32x4*)W; p.res = nullptr; p.h_out = nullptr; p.out_f32 = out_f32; p.M = M; p.N = N; p.ldx = ldx; p.dbg = dbg;
-  const int cols = (N % 6 == 0) ? 3 : 4, wgs = N / (cols * 2), rg = (M + 3) / 4;
-  hipStream_t stream = (hipStream_t)s;
-#define CD2_LAUNCH(RG_, COLS_)                                                                                                           \
-  do {                                                                                                                                   \
-    if (dbg) hipLaunchKernelGGL((chain_down_kernel<7, 5, RG_, COLS_, 2, 2, true>), dim3(wgs, 2), dim3(7 * 64), 0, stream, p);               \
-    else hipLaunchKernelGGL((chain_down_kernel<7, 5, RG_, COLS_, 2, 2, false>), dim3(wgs, 2), dim3(7 * 64), 0, stream, p);                  \
-    VL_LAUNCH_CHECK();                                                                                                                   \
-    return 0;                                                                                                                            \
-  } while (0)
-  if (rg == 1) { if (cols == 3) CD2_LAUNCH(1, 3); else CD2_LAUNCH(1, 4); }
-  if (rg == 2) { if (cols == 3) CD2_LAUNCH(2, 3); else CD2_LAUNCH(2, 4); }
-#undef CD2_LAUNCH
-  vlaser_set_error("vlaser_chain_down2: no variant");
   return -1;
 }
 

@@ -230,9 +230,6 @@ __global__ __launch_bounds__(SKT) void skinny_kernel(SkinnyP p) {
   constexpr int UE = TPU == 1 ? 5 : 3;          // EARLY: units held in registers at once (16-row units: 1120 / 256 -> 4 or 5 per workgroup)
   constexpr bool EPI16 = (TPU == 1 && EPI == VL_SK_QKV_ROPE);
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef VL_KERNARG_UP_FRONT
-  vl_kernargs_up_front(p);
-#endif
   const VlaserSkinnyArgs& a = p.a;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, g = lane >> 4;
@@ -754,10 +751,6 @@ static int launch(const VlaserSkinnyArgs* a, hipStream_t stream) {
     vlaser_set_error("vlaser_skinny: tiles_per_unit = 1 is built for PLAIN + PARTIAL (5 / 7 K-steps per wave), ATTN + PARTIAL (2 / 3) and NORM + SWIGLU / QKV_ROPE (3 / 6)");
     return -1;
   }
-  if (a->tiles_per_unit == 6) {      // 96-row units (r01: 12.3 vs 11.2 us for the expert's gate/up, and 380 B of scratch): removed in r05
-    vlaser_set_error("vlaser_skinny: tiles_per_unit = 6 is no longer built (slower than 32-row units and the only variant that spilled)");
-    return -1;
-  }
   switch (ns) {
     case 1: return launch_ns<PRO, EPI, 2, 1>(a, stream);
     case 2: return launch_ns<PRO, EPI, 2, 2>(a, stream);
@@ -786,9 +779,9 @@ extern "C" int vlaser_skinny(int pro, int epi, const VlaserSkinnyArgs* a, vl_str
   VL_CHECK(a->k_splits >= 1 && a->K % (a->k_splits * 32 * SKW) == 0, "vlaser_skinny: K=%d not divisible by k_splits*%d (k_splits=%d)", a->K,
            32 * SKW, a->k_splits);
   VL_CHECK(a->tiles_per_unit == 0 || a->tiles_per_unit == 1 || a->tiles_per_unit == 2, "vlaser_skinny: tiles_per_unit must be 1 or 2");
-  VL_CHECK(a->N % (a->tiles_per_unit == 6 ? 96 : (a->tiles_per_unit == 1 ? 16 : 32)) == 0,
+  VL_CHECK(a->N % (a->tiles_per_unit == 1 ? 16 : 32) == 0,
            "vlaser_skinny: N=%d must be a multiple of the unit height (pack_skinny pads the weight rows; pass n_valid)", a->N);
-  VL_CHECK(a->n_valid <= a->N && (a->n_valid <= 0 || a->n_valid > a->N - (a->tiles_per_unit == 6 ? 96 : (a->tiles_per_unit == 1 ? 16 : 32))),
+  VL_CHECK(a->n_valid <= a->N && (a->n_valid <= 0 || a->n_valid > a->N - (a->tiles_per_unit == 1 ? 16 : 32)),
            "vlaser_skinny: n_valid must lie in the last unit");
   VL_CHECK(((uintptr_t)a->W & 15) == 0 && ((uintptr_t)a->x & 15) == 0, "vlaser_skinny: alignment");
   VL_CHECK((size_t)a->M * (a->K / a->k_splits * 2 + 16) <= 120000, "vlaser_skinny: activation tile does not fit in LDS");

@@ -40,6 +40,7 @@ class QwenLayerWeights:
         self.ln_post = g('post_attention_layernorm.weight')
         if gemm:
             self.wqkv, self.wo, self.wgu, self.wdown = wqkv, wo, wgu, wdown
+        self.sk_down4 = None
         if skinny:
             self.bqkv_sk = self.bqkv
             if 'qkv16' in opts:           # 16-row lane-local units (r03): 2x the workgroups on the q/k/v GEMV
@@ -49,19 +50,68 @@ class QwenLayerWeights:
             else:
                 self.sk_qkv = ops.pack_skinny(wqkv, 1)
             self.sk_o = ops.pack_skinny(wo, ks_o, tpu_o)
-            # wide output + short K (action expert: 17920 x 768): 96-row units (tpu = 6) measured slower on MI355X (12.3 vs 11.2 us): kept in
-            # the kernel, not used; 16-row lane-local units ('gu16', r03) balance 1120 units over 256 workgroups (80 vs 96 rows on the longest)
+            # wide output + short K (action expert: 17920 x 768): 96-row units (tpu = 6) measured slower on MI355X (12.3 vs 11.2 us) and left
+            # the kernel in r05; 16-row lane-local units ('gu16', r03) balance 1120 units over 256 workgroups (80 vs 96 rows on the longest)
             if 'gu16' in opts:
                 self.sk_gu = ops.pack_skinny(ops.pack_gate_up8(g('mlp.gate_proj.weight'), g('mlp.up_proj.weight')), 1, 1)
             else:
                 self.sk_gu = ops.pack_skinny(wgu, 1, 2)
             self.sk_down = ops.pack_skinny(wdown, ks_down, tpu_down, k_pad=i_pad)
             # 'chain' (r05, csrc/chain.hip): the down projection without cross-workgroup split-K (4 output columns per workgroup over the whole K) publishes the next
-            # layer's residual stream as bf16; needs the 16-row q/k/v packing and the MLP width the kernel is built for
-            ok4 = 'chain' in opts and 'qkv16' in opts and wdown.shape[1] == ops.DOWN4_WAVES * ops.DOWN4_LOADS * 128
-            self.sk_down4 = ops.pack_down4(wdown) if (ok4 and (wdown.shape[0] % 3 == 0 or wdown.shape[0] % 4 == 0)) else None
-            # 'down2' (with 'chain'): the down projection as two K halves on 256 six-column workgroups leaving two fp32 slabs (vlaser_chain_down2) that the q/k/v launch reduces
-            self.sk_down42 = ops.pack_down4(wdown, k_splits=2) if (ok4 and 'down2' in opts and (wdown.shape[0] % 6 == 0 or wdown.shape[0] % 8 == 0)) else None
+            # layer's residual stream as bf16
+            if chain_packed(opts, wdown.shape[0], wdown.shape[1]):
+                self.sk_down4 = ops.pack_down4(wdown)
+
+
+def chain_packed(opts, H, I):
+    """Whether a stack carries the packings of the csrc/chain.hip kernels: asked for ('chain'), with the 16-row q/k/v units they read ('qkv16'), at the widths
+    ops.pack_down4 / vlaser_chain_down serve."""
+    return 'chain' in opts and 'qkv16' in opts and I == ops.DOWN4_WAVES * ops.DOWN4_LOADS * 128 and (H % 3 == 0 or H % 4 == 0)
+
+
+def stack_geometry(llm: LLMConfig):
+    """(tpu_o, ks_o, tpu_down, ks_down, I_pad): tiles per unit and split-K factors of the o / down projections of the weight-streaming kernels, and the padded MLP width."""
+    H, I = llm.hidden_size, llm.intermediate_size
+    nqd = llm.num_attention_heads * llm.head_dim
+    # o_proj on 16-row units where the kernel has the variant: the same ~144 workgroups with half the split-K slabs for the
+    # gate/up prologue to sum (chunk time unchanged, the dominant gate/up GEMV 8.9 -> 8.6 us; same-box A/B)
+    ks16o = ops.pick_k_splits(nqd, H, rows_per_unit=16)
+    tpu_o = 1 if (ks16o is not None and nqd // (ks16o * 256) in (2, 3)) else 2
+    ks_o = ks16o if tpu_o == 1 else ops.skinny_geometry(nqd, H)[1]
+    # down_proj (narrow output, long K): 16-row units double the workgroups that stream it (48 units x 5 splits = 240 for the expert)
+    # when the kernel has that variant (5 or 7 K-steps per wave); measured +0.9 % chunks/s over 32-row units x 7 splits
+    ks16 = ops.pick_k_splits(I, H, rows_per_unit=16)
+    tpu_down = 1 if (ks16 is not None and I // (ks16 * 256) in (5, 7)) else 2
+    I_pad, ks32 = ops.skinny_geometry(I, H)            # widths that do not factor (Vlaser-8B: 18944) are zero-padded: act buffer + down weight
+    return tpu_o, ks_o, tpu_down, (ks16 if tpu_down == 1 else ks32), I_pad
+
+
+def path_geometry(llm: LLMConfig, opts):
+    """What layer_path reads of a stack, as integers and booleans: the widths, and the rows (ops.skinny_rows, as ops.pack_skinny pads them) and units of the
+    q/k/v, gate/up and o matrices as QwenLayerWeights packs them under `opts` (QwenStack checks its packed layers against this)."""
+    H, I, nq, nkv, hd = llm.hidden_size, llm.intermediate_size, llm.num_attention_heads, llm.num_key_value_heads, llm.head_dim
+    tpu_o, ks_o = stack_geometry(llm)[:2]
+    tpu_gu = 1 if 'gu16' in opts else 2
+    return dict(chain_packed=chain_packed(opts, H, I), H=H, I=I, n_qkv=ops.skinny_rows((nq + 2 * nkv) * hd, 1 if 'qkv16' in opts else 2),
+                n_gu=ops.skinny_rows(2 * I, tpu_gu), tpu_gu=tpu_gu, n_o=ops.skinny_rows(H, tpu_o), tpu_o=tpu_o, ks_o=ks_o, nq=nq, nkv=nkv, hd=hd)
+
+
+def layer_path(*, chain_packed, H, I, n_qkv, n_gu, tpu_gu, n_o, tpu_o, ks_o, nq, nkv, hd, act_width, M, tok_per_batch, kv_len, n_partials=0, input_is_hB=False,
+               skip_post_attn=False, dense_mask=False):
+    """(chain, chain_ao) of one skinny_layer call -- the ONE place that decides between the kernels of csrc/chain.hip and of csrc/skinny.hip (and the only caller of
+    the library's *_supported predicates).  Integers and booleans in (path_geometry of the stack + the call), no tensors.
+    chain: q/k/v, gate/up and down on the latency-built kernels -- the layer takes a residual stream that is already reduced (n_partials == 0: the action encoder's output,
+    or what the previous layer's vlaser_chain_down published; not hB, which this layer's gate/up launch overwrites while its other workgroups still read their input) and hands
+    on (hC, None, 0).
+    chain_ao: attention + o_proj on the one-wave-per-split attention / bf16-partial merge pair, when the key count gives a split count they are built for.
+    A dense additive mask (ABI 8) is served by the chain attention only (every <= 16-row launch of the VLA at its shipped widths): NotImplementedError elsewhere."""
+    chain = (chain_packed and act_width == I and n_partials == 0 and not input_is_hB
+             and ops.chain_qkv_supported(M, n_qkv, H) and ops.chain_gu_supported(M, n_gu, H, ks_o, tpu_gu) and ops.chain_down_supported(M, H, I))
+    chain_ao = (chain and not skip_post_attn and tpu_o == 1 and tok_per_batch * (nq // nkv) <= 32
+                and ops.chain_oproj_supported(M, n_o, nq * hd, ks_o, ops.chain_attn_splits(kv_len), nq // nkv))
+    if dense_mask and not (chain_ao or (chain and skip_post_attn)):
+        raise NotImplementedError('dense additive masks need the chain attention (hidden 768 / 1536, <= 16 rows, group * tokens <= 32)')
+    return chain, chain_ao
 
 
 class QwenStack:
@@ -70,26 +120,18 @@ class QwenStack:
     def __init__(self, sd, prefix, llm: LLMConfig, device, with_embed=True, with_head=True, gemm=True, skinny=True, opts=()):
         self.llm = llm
         self.opts = tuple(opts)
-        H, I = llm.hidden_size, llm.intermediate_size
-        nqd = llm.num_attention_heads * llm.head_dim
-        # o_proj on 16-row units where the kernel has the variant: the same ~144 workgroups with half the split-K slabs for the
-        # gate/up prologue to sum (chunk time unchanged, the dominant gate/up GEMV 8.9 -> 8.6 us; same-box A/B)
-        ks16o = ops.pick_k_splits(nqd, H, rows_per_unit=16)
-        self.tpu_o = 1 if (ks16o is not None and nqd // (ks16o * 256) in (2, 3)) else 2
-        self.ks_o = ks16o if self.tpu_o == 1 else ops.skinny_geometry(nqd, H)[1]
-        # down_proj (narrow output, long K): 16-row units double the workgroups that stream it (48 units x 5 splits = 240 for the expert)
-        # when the kernel has that variant (5 or 7 K-steps per wave); measured +0.9 % chunks/s over 32-row units x 7 splits
-        ks16 = ops.pick_k_splits(I, H, rows_per_unit=16)
-        self.tpu_down = 1 if (ks16 is not None and I // (ks16 * 256) in (5, 7)) else 2
-        self.I_pad, ks32 = ops.skinny_geometry(I, H)            # widths that do not factor (Vlaser-8B: 18944) are zero-padded: act buffer + down weight
-        self.ks_down = ks16 if self.tpu_down == 1 else ks32
-        self.nqd = nqd
+        self.nqd = llm.num_attention_heads * llm.head_dim
+        self.tpu_o, self.ks_o, self.tpu_down, self.ks_down, self.I_pad = stack_geometry(llm)
         self.layers = [QwenLayerWeights(sd, f'{prefix}model.layers.{i}.', llm, device, self.ks_o, self.ks_down, gemm, skinny, self.tpu_down, self.tpu_o, self.I_pad, self.opts)
                        for i in range(llm.num_hidden_layers)]
         self.norm = _dev(sd[prefix + 'model.norm.weight'], device)
         self.embed = _dev(sd[prefix + 'model.embed_tokens.weight'], device) if with_embed else None
         self.head = _dev(sd[prefix + 'lm_head.weight'], device) if with_head and (prefix + 'lm_head.weight') in sd else None
         self.sk_head = ops.pack_skinny(self.head, 1) if (self.head is not None and skinny) else None
+        self.path = p = path_geometry(llm, self.opts)
+        for lw in self.layers if skinny else ():
+            assert (lw.sk_qkv.N, lw.sk_gu.N, lw.sk_gu.tpu, lw.sk_o.N, lw.sk_o.tpu, lw.sk_down4 is not None) == \
+                (p['n_qkv'], p['n_gu'], p['tpu_gu'], p['n_o'], p['tpu_o'], p['chain_packed']), 'path_geometry disagrees with the packed weights'
 
     @property
     def nq(self):
@@ -311,106 +353,83 @@ def skinny_layer(stack: QwenStack, lw: QwenLayerWeights, sb: SkinnyBuffers, h_in
                  first_tok_kv_len=0, skip=(), dense_mask=None):
     """One decoder layer over M = batch*tok_per_batch <= 16 rows with the weight-streaming kernels (5 launches).
     Input residual = h_in + sum(partials) (partials = down_proj slabs of the previous layer).  Returns
-    (h, partials, n_partials) describing this layer's output residual the same way."""
-    llm = stack.llm
+    (h, partials, n_partials) describing this layer's output residual the same way.
+    The kernel path (layer_path), the argument structs and the launch list of a (layer, input buffers, geometry) are built once and re-launched: only the cache slot,
+    the key count and its split factor change from step to step (greedy decode is otherwise host-bound on deciding and struct building)."""
     M = batch * tok_per_batch
-    nq, nkv, hd = stack.nq, stack.nkv, llm.head_dim
-    # the five argument structs of this (layer, input buffers, geometry) are built once and re-launched: only the cache slot,
-    # the key count and its split factor change from step to step (greedy decode is otherwise host-bound on struct building)
-    # (the two fused launches of r03 / r04 -- o_proj -> gate/up with an in-launch hand-off, attention + o_proj in one launch -- lost to the r05 chain kernels below and were
-    # removed from the library: DESIGN.md section 3)
-    nsp = ops.attn_splits(kv_len)
-    # 'chain' (r05): qkv / gate-up / down on the latency-built kernels of csrc/chain.hip -- the layer takes a residual stream that is already reduced (n_partials == 0:
-    # the action encoder's output, or what the previous layer's vlaser_chain_down published) and hands on (hC, None, 0)
-    H_, I_ = llm.hidden_size, llm.intermediate_size
-    down2 = getattr(lw, 'sk_down42', None) is not None and ops.chain_down2_supported(M, H_, I_)
-    from_down2 = n_partials == 2 and partials is not None and partials.data_ptr() == sb.part_d.data_ptr() and down2
-    chain = ('chain' in stack.opts and getattr(lw, 'sk_down4', None) is not None and lw.sk_qkv.tpu == 1
-             and ((n_partials == 0 and h_in.data_ptr() != sb.hB.data_ptr()) or from_down2)
-             and ops.chain_qkv_supported(M, lw.sk_qkv.N, H_) and ops.chain_gu_supported(M, lw.sk_gu.N, H_, stack.ks_o, lw.sk_gu.tpu)
-             and ops.chain_down_supported(M, H_, I_) and sb.act.shape[1] == I_)
-    # ... and attention + o_proj on the one-wave-per-split attention / bf16-partial merge pair when the key count gives the split count they are built for
-    nsp2 = ops.chain_attn_splits(kv_len)
-    chain_ao = (chain and not skip_post_attn and lw.sk_o.tpu == 1 and tok_per_batch * (nq // nkv) <= 32
-                and ops.chain_oproj_supported(M, lw.sk_o.N, nq * hd, stack.ks_o, nsp2, nq // nkv) and 'chain_noao' not in stack.opts)
-    if dense_mask is not None:
-        # general additive masks (ABI 8) are served by the chain attention only (every <= 16-row launch of the VLA at its shipped widths)
-        if not (chain_ao or (chain and skip_post_attn)):
-            raise NotImplementedError('dense additive masks need the chain attention (hidden 768 / 1536, <= 16 rows, group * tokens <= 32)')
-        attn_mode = L.ATTN_DENSE
+    # the key holds what the plan depends on; of kv_len, the path only reads whether the chain attention + o_proj pair is built for its split count (1..16)
     key = (layer, M, tok_per_batch, attn_mode, h_in.data_ptr(), 0 if partials is None else partials.data_ptr(), n_partials,
            0 if valid_len is None else valid_len.data_ptr(), pos_ids.data_ptr(), cache.k.data_ptr(), skip_post_attn, first_tok_kv_len,
-           chain, chain_ao, down2, 0 if dense_mask is None else dense_mask.data_ptr())
+           0 < ops.chain_attn_splits(kv_len) <= 16, 0 if dense_mask is None else dense_mask.data_ptr())
     plan = sb.plans.get(key)
     if plan is None:
-        ks, vs = cache.strides()
-        plan = SimpleNamespace()
-        plan.qkv = ops.skinny_args(h_in, lw.sk_qkv, M, partials=partials, n_partials=n_partials, norm_w=lw.ln_in, eps=llm.rms_norm_eps,
-                                   h_out=sb.hA, bias=lw.bqkv_sk, q_out=sb.q, k_cache=cache.k[layer], vt_cache=cache.vt[layer], rope_cos=rope[0],
-                                   rope_sin=rope[1], pos_ids=pos_ids, n_q_heads=nq, n_kv_heads=nkv, s_max=cache.s_max,
-                                   tok_per_batch=tok_per_batch, slot_base=slot_base)
-        plan.attn = ops.attn_skinny_args(sb.q, cache.k[layer], cache.vt[layer], sb.attn_parts, batch, tok_per_batch, kv_len, nq, nkv, hd,
-                                         (tok_per_batch * nq * hd, hd, nq * hd), ks, vs, cache.s_max, hd ** -0.5, attn_mode, 1,
-                                         valid_len=valid_len, blk_start=blk_start, first_tok_kv_len=first_tok_kv_len)
-        if not skip_post_attn:
-            plan.o = ops.skinny_args(None, lw.sk_o, M, out_f32=sb.part_o, attn_m=sb.attn_parts[0], attn_l=sb.attn_parts[1],
-                                     attn_o=sb.attn_parts[2], attn_splits=1, attn_group=nq // nkv, attn_nq=tok_per_batch)
-            if chain_ao:
-                plan.attn = ops.attn_skinny_args(sb.q, cache.k[layer], cache.vt[layer], (sb.chain_parts[0], sb.chain_parts[0], sb.chain_parts[1]), batch, tok_per_batch,
-                                                 kv_len, nq, nkv, hd, (tok_per_batch * nq * hd, hd, nq * hd), ks, vs, cache.s_max, hd ** -0.5, attn_mode, nsp2,
-                                                 valid_len=valid_len, blk_start=blk_start, first_tok_kv_len=first_tok_kv_len, dense_mask=dense_mask)
-                plan.o = ops.skinny_args(None, lw.sk_o, M, out_f32=sb.part_o, attn_m=sb.chain_parts[0], attn_o=sb.chain_parts[1], attn_splits=nsp2,
-                                         attn_group=nq // nkv, attn_nq=tok_per_batch)
-            # (chain: vlaser_chain_qkv leaves no rounded copy of the residual stream behind -- its input already IS the rounded stream)
-            plan.gu = ops.skinny_args(h_in if (chain and n_partials == 0) else sb.hA, lw.sk_gu, M, partials=sb.part_o, n_partials=stack.ks_o, norm_w=lw.ln_post,
-                                      eps=llm.rms_norm_eps, h_out=sb.hB, out=sb.act, ldo=sb.act.shape[1])
-            plan.down = SimpleNamespace(dbg=None) if chain else ops.skinny_args(sb.act, lw.sk_down, M, out_f32=sb.part_d)
+        plan = _build_plan(stack, lw, sb, h_in, partials, n_partials, cache, layer, rope, pos_ids, batch, tok_per_batch, slot_base, kv_len, attn_mode, valid_len,
+                           blk_start, skip_post_attn, first_tok_kv_len, dense_mask)
         if len(sb.plans) > 4096:         # keys hold buffer addresses of per-call tensors (ragged lengths): bound the cache
             sb.plans.clear()
         sb.plans[key] = plan
-    stream = torch.cuda.current_stream().cuda_stream
+    nsp = ops.chain_attn_splits(kv_len) if plan.chain_ao else ops.attn_splits(kv_len)
     plan.qkv[0].slot_base = slot_base
-    if 'qkv' not in skip:                 # `skip` (bench.py only): in-chain timing of one launch = chain with it - chain without it
-        if chain:
-            ops.launch_chain_qkv(plan.qkv[0], stream)
-        else:
-            ops.launch_skinny(L.PRO_NORM, L.SK_QKV_ROPE, plan.qkv[0], stream)
     a = plan.attn
-    a.kv_len, a.n_splits, a.blk_start = kv_len, (nsp2 if chain_ao else nsp), blk_start
+    a.kv_len, a.n_splits, a.blk_start = kv_len, nsp, blk_start
+    if not skip_post_attn:
+        plan.o[0].attn_splits = nsp          # (the key count, hence the split count, moves from step to step in an eager decode)
+    stream = torch.cuda.current_stream().cuda_stream
+    for name, launch, args in plan.launches:
+        if name not in skip:                  # `skip` (bench.py only): in-chain timing of one launch = chain with it - chain without it
+            launch(*args, stream)
+    return plan.result
+
+
+def _chain_down(sb, W4, M, H, I, down, stream):          # `down.dbg`: read at launch time, tools set it after the plan is built
+    ops.chain_down(sb.act, W4, sb.hB, sb.hC, M, H, I, dbg=down.dbg, stream=stream)
+
+
+def _build_plan(stack, lw, sb, h_in, partials, n_partials, cache, layer, rope, pos_ids, batch, tok_per_batch, slot_base, kv_len, attn_mode, valid_len, blk_start,
+                skip_post_attn, first_tok_kv_len, dense_mask):
+    """The plan of one skinny_layer key: .chain / .chain_ao (layer_path), the argument structs .qkv / .attn / .o / .gu / .down (tools set their `dbg`), .launches =
+    [(name, launch, args)] in launch order, run as launch(*args, stream) (tuples, not closures over the plan: a cleared cache frees its plans at once), .result = the (h, partials, n_partials) the layer hands on.
+    (The two fused launches of r03 / r04 -- o_proj -> gate/up with an in-launch hand-off, attention + o_proj in one launch -- lost to the r05 chain kernels and were
+    removed from the library: DESIGN.md section 3)"""
+    llm = stack.llm
+    M = batch * tok_per_batch
+    nq, nkv, hd = stack.nq, stack.nkv, llm.head_dim
+    H, I = llm.hidden_size, llm.intermediate_size
+    chain, chain_ao = layer_path(**stack.path, act_width=sb.act.shape[1], M=M, tok_per_batch=tok_per_batch, kv_len=kv_len, n_partials=n_partials,
+                                 input_is_hB=h_in.data_ptr() == sb.hB.data_ptr(), skip_post_attn=skip_post_attn, dense_mask=dense_mask is not None)
+    if dense_mask is not None:
+        attn_mode = L.ATTN_DENSE
+    ks, vs = cache.strides()
+    plan = SimpleNamespace(chain=chain, chain_ao=chain_ao)
+    plan.qkv = ops.skinny_args(h_in, lw.sk_qkv, M, partials=partials, n_partials=n_partials, norm_w=lw.ln_in, eps=llm.rms_norm_eps,
+                               h_out=sb.hA, bias=lw.bqkv_sk, q_out=sb.q, k_cache=cache.k[layer], vt_cache=cache.vt[layer], rope_cos=rope[0],
+                               rope_sin=rope[1], pos_ids=pos_ids, n_q_heads=nq, n_kv_heads=nkv, s_max=cache.s_max,
+                               tok_per_batch=tok_per_batch, slot_base=slot_base)
+    # chain_ao: (m, l) pairs + normalised bf16 rows per split; else flash-decoding partials that the o_proj prologue merges straight into its activation tile
+    attn_parts = (sb.chain_parts[0], sb.chain_parts[0], sb.chain_parts[1]) if chain_ao else sb.attn_parts
+    plan.attn = ops.attn_skinny_args(sb.q, cache.k[layer], cache.vt[layer], attn_parts, batch, tok_per_batch, kv_len, nq, nkv, hd,
+                                     (tok_per_batch * nq * hd, hd, nq * hd), ks, vs, cache.s_max, hd ** -0.5, attn_mode, 1,
+                                     valid_len=valid_len, blk_start=blk_start, first_tok_kv_len=first_tok_kv_len, dense_mask=dense_mask if chain_ao else None)
+    plan.launches = [('qkv', ops.launch_chain_qkv, (plan.qkv[0],)) if chain else ('qkv', ops.launch_skinny, (L.PRO_NORM, L.SK_QKV_ROPE, plan.qkv[0]))]
+    if skip_post_attn:          # only this layer's K / V are needed (written by the qkv launch); the chain q/k/v leaves no rounded copy of its input behind -- it IS the rounded stream
+        plan.result = (h_in if chain else sb.hA, None, 0)
+        return plan
+    if chain_ao:
+        plan.o = ops.skinny_args(None, lw.sk_o, M, out_f32=sb.part_o, attn_m=sb.chain_parts[0], attn_o=sb.chain_parts[1], attn_splits=1,
+                                 attn_group=nq // nkv, attn_nq=tok_per_batch)
+        plan.launches += [('attn', ops.launch_chain_attn, (plan.attn,)), ('o', ops.launch_chain_oproj, (plan.o[0],))]
+    else:
+        plan.o = ops.skinny_args(None, lw.sk_o, M, out_f32=sb.part_o, attn_m=sb.attn_parts[0], attn_l=sb.attn_parts[1],
+                                 attn_o=sb.attn_parts[2], attn_splits=1, attn_group=nq // nkv, attn_nq=tok_per_batch)
+        plan.launches += [('attn', ops.launch_attn_skinny, (plan.attn,)), ('o', ops.launch_skinny, (L.PRO_ATTN, L.SK_PARTIAL, plan.o[0]))]
+    plan.gu = ops.skinny_args(h_in if chain else sb.hA, lw.sk_gu, M, partials=sb.part_o, n_partials=stack.ks_o, norm_w=lw.ln_post,
+                              eps=llm.rms_norm_eps, h_out=sb.hB, out=sb.act, ldo=sb.act.shape[1])
     if chain:
-        if skip_post_attn:
-            return h_in, None, 0
-        if chain_ao:
-            if 'attn' not in skip:
-                ops.launch_chain_attn(a, stream)
-            plan.o[0].attn_splits = nsp2          # (the key count, hence the split count, moves from step to step in an eager decode)
-            if 'o' not in skip:
-                ops.launch_chain_oproj(plan.o[0], stream)
-        else:
-            if 'attn' not in skip:
-                ops.launch_attn_skinny(a, stream)
-            plan.o[0].attn_splits = nsp
-            if 'o' not in skip:
-                ops.launch_skinny(L.PRO_ATTN, L.SK_PARTIAL, plan.o[0], stream)
-        if 'gu' not in skip:
-            ops.launch_chain_gu(plan.gu[0], stream)
-        if down2:
-            if 'down' not in skip:
-                ops.chain_down2(sb.act, lw.sk_down42, sb.part_d, M, H_, I_, dbg=plan.down.dbg, stream=stream)
-            return sb.hB, sb.part_d, 2
-        if 'down' not in skip:
-            ops.chain_down(sb.act, lw.sk_down4, sb.hB, sb.hC, M, H_, I_, dbg=plan.down.dbg, stream=stream)
-        return sb.hC, None, 0
-    if skip_post_attn:          # only this layer's K / V are needed (written by the qkv launch above)
-        return sb.hA, None, 0
-    if 'attn' not in skip:
-        ops.launch_attn_skinny(a, stream)
-    # o_proj: the prologue merges the attention split partials (flash-decoding) straight into its activation tile
-    plan.o[0].attn_splits = nsp
-    if 'o' not in skip:
-        ops.launch_skinny(L.PRO_ATTN, L.SK_PARTIAL, plan.o[0], stream)
-    if 'gu' not in skip:
-        ops.launch_skinny(L.PRO_NORM, L.SK_SWIGLU, plan.gu[0], stream)
-    if 'down' not in skip:
-        ops.launch_skinny(L.PRO_PLAIN, L.SK_PARTIAL, plan.down[0], stream)
-    return sb.hB, sb.part_d, stack.ks_down
+        plan.down = SimpleNamespace(dbg=None)
+        plan.launches += [('gu', ops.launch_chain_gu, (plan.gu[0],)), ('down', _chain_down, (sb, lw.sk_down4, M, H, I, plan.down))]
+        plan.result = (sb.hC, None, 0)
+    else:
+        plan.down = ops.skinny_args(sb.act, lw.sk_down, M, out_f32=sb.part_d)
+        plan.launches += [('gu', ops.launch_skinny, (L.PRO_NORM, L.SK_SWIGLU, plan.gu[0])), ('down', ops.launch_skinny, (L.PRO_PLAIN, L.SK_PARTIAL, plan.down[0]))]
+        plan.result = (sb.hB, sb.part_d, stack.ks_down)
+    return plan

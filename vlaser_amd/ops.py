@@ -285,6 +285,11 @@ SK_WAVES = 8
 SK_STEPS = (1, 2, 3, 4, 5, 6, 7, 8, 14, 16)      # K-steps (of 32) per wave the kernel is built for; 14 / 16 = two chunks of 7 / 8
 
 
+def skinny_rows(N, tpu):
+    """Rows of a PackedW of N outputs: whole units of 16 * tpu rows."""
+    return -(-N // (16 * tpu)) * 16 * tpu
+
+
 def pack_skinny(W, k_splits=1, tpu=2, k_pad=None):
     """Row-major [N,K] bf16 -> PackedW.  Lane (r = l&15, g = l>>4) of wave w, K-step s, tile t of unit u, split ks holds
     W[u*32 + t*16 + r, ks*kb + w*kw + s*32 + g*8 : +8]; each wave-level load is a contiguous 1 KiB.  k_pad > K appends zero
@@ -294,8 +299,7 @@ def pack_skinny(W, k_splits=1, tpu=2, k_pad=None):
         W = torch.cat([W, torch.zeros(N, k_pad - K, dtype=W.dtype, device=W.device)], 1)
         K = k_pad
     assert K % (k_splits * 32 * SK_WAVES) == 0, (K, k_splits)
-    rpu = 16 * tpu
-    Np = (N + rpu - 1) // rpu * rpu
+    rpu, Np = 16 * tpu, skinny_rows(N, tpu)
     if Np != N:
         W = torch.cat([W, torch.zeros(Np - N, K, dtype=W.dtype, device=W.device)], 0)
     ns = K // (k_splits * SK_WAVES * 32)
@@ -342,32 +346,14 @@ def chain_down_geometry(N):
     return wgs, c.value, g.value
 
 
-def pack_down4(W, nw=DOWN4_WAVES, nl=DOWN4_LOADS, k_splits=1):
-    """down_proj.weight [N, K] -> [K split][workgroup][nw waves][loads][groups][16 blocks][cols][8] bf16 for vlaser_chain_down (k_splits = 1) / vlaser_chain_down2
-    (k_splits = 2: two K halves, always 2 column groups per workgroup): block b, column i of group c of wave w, load l holds
-    W[(wg groups + c) cols + i, kh K/k_splits + (w loads + l) 128 + 8 b : + 8] -- one contiguous 16 x cols x 16 bytes per wave-level load, one contiguous stream per workgroup."""
+def pack_down4(W, nw=DOWN4_WAVES, nl=DOWN4_LOADS):
+    """down_proj.weight [N, K] -> [workgroup][nw waves][loads][groups][16 blocks][cols][8] bf16 for vlaser_chain_down: block b, column i of group c of wave w, load l holds
+    W[(wg groups + c) cols + i, (w loads + l) 128 + 8 b : + 8] -- one contiguous 16 x cols x 16 bytes per wave-level load, one contiguous stream per workgroup."""
     N, K = W.shape
-    if k_splits == 1:
-        wgs, cols, groups = chain_down_geometry(N)
-    else:
-        assert k_splits == 2 and nl % 2 == 0 and (N % 6 == 0 or N % 8 == 0), (N, K, k_splits)
-        cols, groups = (3 if N % 6 == 0 else 4), 2
-        wgs = N // (cols * groups)
-    nlk = nl // k_splits
+    wgs, cols, groups = chain_down_geometry(N)
     assert N == wgs * cols * groups and K == nw * nl * 128, (N, K)
-    v = W.view(wgs, groups, cols, k_splits, nw, nlk, 16, 8)                # [wg, c, i, kh, w, l, b, e]
-    return v.permute(3, 0, 4, 5, 1, 6, 2, 7).contiguous().reshape(-1)      # [kh, wg, w, l, c, b, i, e]
-
-
-def chain_down2(x, W42, out_f32, M, N, K, dbg=None, stream=None):
-    """out_f32[2, M, N] = the two K halves of x[M, :K] @ W^T (fp32, no residual), W42 = pack_down4(W, k_splits=2)."""
-    assert x.dtype == BF16 and out_f32.dtype == torch.float32 and x.stride(-1) == 1 and out_f32.numel() >= 2 * M * N
-    L.check(L.lib().vlaser_chain_down2(x.data_ptr(), x.stride(0), W42.data_ptr(), out_f32.data_ptr(), M, N, K, dbg if isinstance(dbg, int) else _p(dbg),
-                                       _stream() if stream is None else stream), 'vlaser_chain_down2')
-
-
-def chain_down2_supported(M, N, K):
-    return bool(L.lib().vlaser_chain_down2_supported(M, N, K)) and bool(L.lib().vlaser_chain_qkv2_supported(M, 128, 768 if N == 768 else N))
+    v = W.view(wgs, groups, cols, nw, nl, 16, 8)                           # [wg, c, i, w, l, b, e]
+    return v.permute(0, 3, 4, 1, 5, 2, 6).contiguous().reshape(-1)         # [wg, w, l, c, b, i, e]
 
 
 def chain_qkv_supported(M, N, K):
