@@ -226,6 +226,7 @@ typedef struct {
   /* VL_PRO_ATTN: x[m = b*nq+tok][h*128+d] = sum_s o_s e^(m_s-M) / sum_s l_s e^(m_s-M) */
   const float* attn_m; const float* attn_l; const float* attn_o; int attn_splits, attn_group, attn_nq;
   unsigned long long* dbg; /* optional: per-block timestamps [grid][8] (wall_clock64, 100 MHz) for kernel tuning */
+  const float* w_scale;    /* vlaser_chain_gu_w8 only (appended, ABI 8 unchanged: nothing else reads it): fp32 [N] row scales of the e4m3 weights, in the packed row order of W */
 } VlaserSkinnyArgs;
 
 int vlaser_skinny(int prologue, int epi, const VlaserSkinnyArgs* args, vl_stream_t stream);
@@ -257,6 +258,21 @@ int vlaser_chain_down_geometry(int N, int* cols, int* groups);      /* returns t
 int vlaser_chain_qkv(const VlaserSkinnyArgs* args, vl_stream_t stream);
 int vlaser_chain_gu(const VlaserSkinnyArgs* args, vl_stream_t stream);
 int vlaser_chain_down(const void* x, int ldx, const void* W, const void* res, void* h_out, int M, int N, int K, unsigned long long* dbg, vl_stream_t stream);
+/* ---- (ABI 8, additive) the action expert's MLP with one-byte weights: the two launches above with W as OCP e4m3 codes (e4m3fn, not fnuz) and one fp32 scale per weight row,
+ * W[n][k] = scale[n] * e4m3(code[n][k]) (ops.quantize_rows_e4m3: power-of-two scales).  Stands for the quantized linears the reference loads its action model with
+ * (Vlaser_VLA/Simpler/src/model/lora.py:84-97, the `quantize` branches of the linear-layer factory, :216-230 the quantised Linear; `quantize:` / `use_quantize:` in config/eval/bridge_internvl_448.yaml:50) at the call sites of the bf16 forms
+ * (joint_model.py:140-232, the MLP of each action-expert layer).  Weight-only: the codes become bf16 in registers, the bf16 MFMAs and every summation order are those of
+ * vlaser_chain_gu / vlaser_chain_down, and the scale multiplies the reduced fp32 sum once, before the first rounding -- with power-of-two scales the outputs are
+ * bit-identical to the bf16 forms run on the dequantised weights.
+ *   vlaser_chain_gu_w8  : args as vlaser_chain_gu with tiles_per_unit = 1, W = ops.pack_gate_up8_e4m3 (per unit and wave: 64 x 16 bytes = the lanes' fragments of K-steps 0
+ *                         and 1, then 64 x 8 bytes = K-step 2), w_scale = fp32 [N], 16-byte aligned;  K = 768, 3 producer slabs, 5 units per workgroup
+ *   vlaser_chain_down_w8: as vlaser_chain_down with W = ops.pack_down4_e4m3 ([workgroup][7 waves][5 load pairs][groups][16 blocks][cols][2 loads][8]) and
+ *                         w_scale = ops.pack_down4_scales: fp32 [N / cols][4], a column group's scales in one 16-byte load (the fourth repeats the third where cols = 3)
+ * Null or misaligned scales and unsupported shapes are refused on the host, before any launch. */
+int vlaser_chain_gu_w8_supported(int M, int N, int K, int n_partials, int tiles_per_unit);
+int vlaser_chain_gu_w8(const VlaserSkinnyArgs* args, vl_stream_t stream);
+int vlaser_chain_down_w8_supported(int M, int N, int K);
+int vlaser_chain_down_w8(const void* x, int ldx, const void* W, const float* w_scale, const void* res, void* h_out, int M, int N, int K, unsigned long long* dbg, vl_stream_t stream);
 /* (ABI 8: four entry points left without a change of number, no struct and no remaining prototype changed: vlaser_chain_down2, vlaser_chain_down2_supported,
  * vlaser_chain_qkv2_supported -- the down projection as two K halves leaving fp32 slabs for q/k/v to fold, measured equal inside the chunk and never shipped --
  * and vlaser_chain_qkv_set_waves, a process-global switch that only that comparison needed.  profiles/HISTORY.md keeps the measurement.) */

@@ -34,7 +34,7 @@ class SkinnyArgs(C.Structure):
                 ('out', vp), ('ldo', i32), ('bias', vp), ('q_out', vp), ('k_cache', vp), ('vt_cache', vp),
                 ('rope_cos', vp), ('rope_sin', vp), ('pos_ids', vp), ('n_q_heads', i32), ('n_kv_heads', i32),
                 ('s_max', i32), ('tok_per_batch', i32), ('slot_base', i32), ('attn_m', vp), ('attn_l', vp), ('attn_o', vp),
-                ('attn_splits', i32), ('attn_group', i32), ('attn_nq', i32), ('dbg', vp)]
+                ('attn_splits', i32), ('attn_group', i32), ('attn_nq', i32), ('dbg', vp), ('w_scale', vp)]
 
 
 class VlaStageArgs(C.Structure):
@@ -76,6 +76,10 @@ _SIGS = {
     'vlaser_chain_oproj': [C.POINTER(SkinnyArgs), vp],
     'vlaser_chain_gu': [C.POINTER(SkinnyArgs), vp],
     'vlaser_chain_down': [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp],
+    'vlaser_chain_gu_w8_supported': [i32, i32, i32, i32, i32],
+    'vlaser_chain_gu_w8': [C.POINTER(SkinnyArgs), vp],
+    'vlaser_chain_down_w8_supported': [i32, i32, i32],
+    'vlaser_chain_down_w8': [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp],
     'vlaser_layernorm': [vp, vp, vp, vp, i32, i32, f32, vp],
     'vlaser_rmsnorm': [vp, vp, vp, i32, i32, f32, vp],
     'vlaser_im2col': [vp, vp, i32, i32, i32, vp],

@@ -24,10 +24,19 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 __device__ __forceinline__ int ch_fdiv(int x, float inv_d) { return (int)(((float)x + 0.5f) * inv_d); }
 
+// W8 forms (ops.quantize_rows_e4m3): the MLP weights arrive as OCP e4m3 codes, one byte each, and become the bf16 MFMA operand in registers -- every finite e4m3 value is
+// exact in bf16, so the MFMAs, their order and the reductions are those of the bf16 form; the row's fp32 scale multiplies the reduced sum once, in the epilogue.
+// Two dwords = 8 codes in memory order -> the 8 bf16 of one 16-byte bf16 fragment.
+typedef __attribute__((ext_vector_type(2))) __bf16 ch_bf16x2;
+__device__ __forceinline__ uint32_t ch_e4m3x2_lo(uint32_t c) { return __builtin_bit_cast(uint32_t, (ch_bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c, 1.0f, false)); }
+__device__ __forceinline__ uint32_t ch_e4m3x2_hi(uint32_t c) { return __builtin_bit_cast(uint32_t, (ch_bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c, 1.0f, true)); }
+__device__ __forceinline__ u32x4 ch_e4m3x8(uint32_t c0, uint32_t c1) { return u32x4{ch_e4m3x2_lo(c0), ch_e4m3x2_hi(c0), ch_e4m3x2_lo(c1), ch_e4m3x2_hi(c1)}; }
+
 // ------------------------------------------------------------------------------------------------------------------ gate / up
 struct ChainGuP {
   const bf16_t* h_in; const float* partials; const bf16_t* norm_w; bf16_t* h_out;
   const u32x4* W; bf16_t* out;
+  const float* w_scale;                 // W8: fp32 [units * 16], packed row order
   int M, ldo, ulo, urem, n_valid;
   float eps, inv_cpr;
   unsigned long long* dbg;
@@ -36,8 +45,12 @@ struct ChainGuP {
 // NS = K / 256 (K-steps of 32 per wave), UE = units per workgroup, SP = split-K slabs of the producer, CPT = 16-byte chunks of the [M, K] residual stream per thread
 // (ceil(M * K / 8 / 512)), TPU = MFMA tiles per unit: 2 = 32 packed rows [gate16 | up16] (ops.pack_gate_up), 1 = 16 rows whose lane group g holds
 // [gate 2g, gate 2g+1, up 2g, up 2g+1] of the unit's 8 activation columns (ops.pack_gate_up8: 1120 instead of 560 units -> 224 workgroups x 5 instead of 187 x 3)
-template <int NS, int UE, int SP, int CPT, int TPU, bool DBG>
+// W8: the unit's weights as e4m3 codes (ops.pack_gate_up8_e4m3).  K = 768 leaves a wave 3 K-steps = 24 bytes per lane and unit: ONE 16-byte load carries the lane's
+// fragments of K-steps 0 and 1, ONE 8-byte load the fragment of K-step 2 (a wave's unit = 64 x 16 bytes, then 64 x 8 bytes: 1536 contiguous bytes) -- two requests per
+// unit instead of three, the same (row, k) elements in every lane, consumed in the same order.
+template <int NS, int UE, int SP, int CPT, int TPU, bool DBG, bool W8 = false>
 __global__ __launch_bounds__(512) void chain_gu_kernel(ChainGuP p) {
+  static_assert(!W8 || (NS == 3 && TPU == 1), "e4m3 weights: built for K = 768 and 16-row units");
   constexpr int K = NS * 256, cpr = K / 8, ngr = cpr / 16, gstride = (ngr + 3) & ~3, XS = K * 2 + 16, NF = TPU * NS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, g = lane >> 4;
@@ -71,6 +84,8 @@ __global__ __launch_bounds__(512) void chain_gu_kernel(ChainGuP p) {
       q[c][2 * u + 1] = *reinterpret_cast<const f32x4*>(pp + 4);
     }
   }
+  f32x4 wsc = {1.f, 1.f, 1.f, 1.f};          // W8: the scales of the four rows whose sums this lane finishes (wave u finishes unit u; waves beyond the workgroup's units shadow its last)
+  if constexpr (W8) wsc = *reinterpret_cast<const f32x4*>(p.w_scale + (size_t)(ustart + min(wave, ucount - 1)) * 16 + g * 4);
   // (hipcc's scheduler moves loads freely -- it does not know that vmcnt retires in issue order: without the fences below it put the norm-weight chunk and two
   //  fragments of unit 0 BEHIND units 1 and 2, so the norm and the first MFMAs waited for the whole stream)
   __builtin_amdgcn_sched_barrier(0);
@@ -79,8 +94,18 @@ __global__ __launch_bounds__(512) void chain_gu_kernel(ChainGuP p) {
   // instead of 2.3).  The barrier waits for instruction issue only -- nobody waits for data here.
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
-  u32x4 w[UE][NF];
-  {
+  u32x4 w[UE][W8 ? 1 : NF];
+  u32x2 w2[W8 ? UE : 1];
+  if constexpr (W8) {
+    const char* wp = reinterpret_cast<const char*>(p.W) + (size_t)wave * 1536;
+#pragma unroll
+    for (int u = 0; u < UE; ++u) {
+      const char* src = wp + (size_t)(ustart + min(u, ucount - 1)) * (8 * 1536);           // a workgroup with fewer units re-requests its last one
+      w[u][0] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src) + lane);
+      w2[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(src + 1024) + lane);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  } else {
     const u32x4* wp = p.W + (size_t)wave * (NF * 64) + lane;
 #pragma unroll
     for (int u = 0; u < UE; ++u) {
@@ -154,8 +179,12 @@ __global__ __launch_bounds__(512) void chain_gu_kernel(ChainGuP p) {
       f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
-        a0 = mfma16(as_bf16x8(w[u][TPU * s]), xf[s], a0);
-        if constexpr (TPU == 2) a1 = mfma16(as_bf16x8(w[u][2 * s + 1]), xf[s], a1);
+        if constexpr (W8) {
+          a0 = mfma16(as_bf16x8(s < 2 ? ch_e4m3x8(w[u][0][2 * (s & 1)], w[u][0][2 * (s & 1) + 1]) : ch_e4m3x8(w2[u][0], w2[u][1])), xf[s], a0);
+        } else {
+          a0 = mfma16(as_bf16x8(w[u][TPU * s]), xf[s], a0);
+          if constexpr (TPU == 2) a1 = mfma16(as_bf16x8(w[u][2 * s + 1]), xf[s], a1);
+        }
       }
       if (u == 0) { if constexpr (DBG) asm volatile("" ::"v"(a0[0])); CH_STAMP(3); }
       float* r = red + (((u * 8 + wave) * TPU) * 64 + lane) * 4;
@@ -191,6 +220,7 @@ __global__ __launch_bounds__(512) void chain_gu_kernel(ChainGuP p) {
     } else {
       if (mok && unit * 16 < p.n_valid) {              // lane group g: [gate 2g, gate 2g+1, up 2g, up 2g+1] -> output columns unit*8 + 2g, + 1
         bf16_t* o = p.out + (size_t)fr * p.ldo + unit * 8 + g * 2;
+        if constexpr (W8) a0 *= wsc;                      // the row scales, on the reduced fp32 sums, before the first rounding
         const float r0 = round_bf16(silu(round_bf16(a0[0]))) * round_bf16(a0[2]);
         const float r1 = round_bf16(silu(round_bf16(a0[1]))) * round_bf16(a0[3]);
         *reinterpret_cast<uint32_t*>(o) = pack_bf16x2(r0, r1);
@@ -206,61 +236,76 @@ __global__ __launch_bounds__(512) void chain_gu_kernel(ChainGuP p) {
   CH_STAMP(5);
 }
 
-template <int NS, int UE, int SP, int CPT, int TPU>
+template <int NS, int UE, int SP, int CPT, int TPU, bool W8 = false>
 static int chain_gu_launch(const ChainGuP& p, int gx, int lds, hipStream_t stream) {
   if (p.dbg) {
-    if (int rc = set_max_lds_once(chain_gu_kernel<NS, UE, SP, CPT, TPU, true>, lds)) return rc;
-    hipLaunchKernelGGL((chain_gu_kernel<NS, UE, SP, CPT, TPU, true>), dim3(gx), dim3(512), lds, stream, p);
+    if (int rc = set_max_lds_once(chain_gu_kernel<NS, UE, SP, CPT, TPU, true, W8>, lds)) return rc;
+    hipLaunchKernelGGL((chain_gu_kernel<NS, UE, SP, CPT, TPU, true, W8>), dim3(gx), dim3(512), lds, stream, p);
   } else {
-    if (int rc = set_max_lds_once(chain_gu_kernel<NS, UE, SP, CPT, TPU, false>, lds)) return rc;
-    hipLaunchKernelGGL((chain_gu_kernel<NS, UE, SP, CPT, TPU, false>), dim3(gx), dim3(512), lds, stream, p);
+    if (int rc = set_max_lds_once(chain_gu_kernel<NS, UE, SP, CPT, TPU, false, W8>, lds)) return rc;
+    hipLaunchKernelGGL((chain_gu_kernel<NS, UE, SP, CPT, TPU, false, W8>), dim3(gx), dim3(512), lds, stream, p);
   }
   VL_LAUNCH_CHECK();
   return 0;
 }
 
 /* tpu = tiles per unit of the packed weights (2: pack_gate_up, 1: pack_gate_up8).
-   ONE list of the built variants {K / 256, units per workgroup, producer slabs, tiles per unit}: the predicate and the dispatch below are both generated from it
-   (the predicate admitted K = 768 / 2 slabs / 2 units per workgroup, which has no instantiation). */
+   ONE list of the built variants {K / 256, units per workgroup, producer slabs, tiles per unit} per weight format: the predicates and the dispatch below are generated from
+   them (the predicate admitted K = 768 / 2 slabs / 2 units per workgroup, which has no instantiation).  The e4m3 list holds what the action expert reaches. */
 #define CG_VARIANTS(X) X(3, 3, 3, 2) X(3, 3, 2, 2) X(6, 3, 2, 2) X(3, 2, 3, 2) X(6, 2, 2, 2) X(3, 5, 3, 1) X(6, 5, 2, 1)
-extern "C" int vlaser_chain_gu_supported(int M, int N, int K, int n_partials, int tpu) {
+#define CG_W8_VARIANTS(X) X(3, 5, 3, 1)
+static int chain_gu_has(int M, int N, int K, int n_partials, int tpu, bool w8) {
   if (M < 1 || M > 16 || K % 256 || (tpu != 1 && tpu != 2) || N < 16 * tpu || N % (16 * tpu)) return 0;
   const int cpt = (M * (K / 8) + 511) / 512;
   if (cpt > 3) return 0;
   const int ns = K / 256, units = N / (16 * tpu), longest = (units + 255) / 256;
 #define CG_HAS(NS_, UE_, SP_, TPU_) if (ns == NS_ && longest == UE_ && n_partials == SP_ && tpu == TPU_) return 1;
-  CG_VARIANTS(CG_HAS)
+  if (w8) { CG_W8_VARIANTS(CG_HAS) } else { CG_VARIANTS(CG_HAS) }
 #undef CG_HAS
   return 0;
 }
+extern "C" int vlaser_chain_gu_supported(int M, int N, int K, int n_partials, int tpu) { return chain_gu_has(M, N, K, n_partials, tpu, false); }
+extern "C" int vlaser_chain_gu_w8_supported(int M, int N, int K, int n_partials, int tpu) { return chain_gu_has(M, N, K, n_partials, tpu, true); }
 
-extern "C" int vlaser_chain_gu(const VlaserSkinnyArgs* a, vl_stream_t s) {
+static int chain_gu_entry(const VlaserSkinnyArgs* a, vl_stream_t s, bool w8) {
   VL_CHECK(a && a->x && a->W && a->norm_w && a->out && a->partials, "vlaser_chain_gu: null operand");
+  VL_CHECK(!w8 || a->w_scale, "vlaser_chain_gu_w8: null w_scale (fp32 row scales of the e4m3 weights, packed row order)");
   const int tpu = a->tiles_per_unit == 1 ? 1 : 2;
   VL_CHECK(a->tiles_per_unit == 2 || a->tiles_per_unit == 0 || a->tiles_per_unit == 1, "vlaser_chain_gu: weights packed in 32-row (pack_gate_up) or 16-row (pack_gate_up8) units");
-  VL_CHECK(a->k_splits == 1 && vlaser_chain_gu_supported(a->M, a->N, a->K, a->n_partials, tpu),
-           "vlaser_chain_gu: built for K = 768 / 1536, 2 or 3 producer slabs, 2-3 (32-row) or 5 (16-row) units per workgroup, M * K / 8 <= 1536 chunks (got M %d N %d K %d slabs %d)", a->M, a->N,
-           a->K, a->n_partials);
-  VL_CHECK(((uintptr_t)a->W & 15) == 0 && ((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->partials & 15) == 0 && ((uintptr_t)a->out & 7) == 0 && a->ldo % 4 == 0, "vlaser_chain_gu: alignment");
+  if (w8)
+    VL_CHECK(a->k_splits == 1 && chain_gu_has(a->M, a->N, a->K, a->n_partials, tpu, true),
+             "vlaser_chain_gu_w8: built for K = 768, 3 producer slabs, 5 16-row units per workgroup, M * K / 8 <= 1536 chunks (got M %d N %d K %d slabs %d tiles per unit %d)", a->M, a->N, a->K,
+             a->n_partials, tpu);
+  else
+    VL_CHECK(a->k_splits == 1 && chain_gu_has(a->M, a->N, a->K, a->n_partials, tpu, false),
+             "vlaser_chain_gu: built for K = 768 / 1536, 2 or 3 producer slabs, 2-3 (32-row) or 5 (16-row) units per workgroup, M * K / 8 <= 1536 chunks (got M %d N %d K %d slabs %d)", a->M, a->N,
+             a->K, a->n_partials);
+  VL_CHECK(((uintptr_t)a->W & 15) == 0 && ((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->partials & 15) == 0 && ((uintptr_t)a->out & 7) == 0 && a->ldo % 4 == 0 &&
+               (!w8 || ((uintptr_t)a->w_scale & 15) == 0),
+           "vlaser_chain_gu: alignment");
   const int n_valid = a->n_valid > 0 ? a->n_valid : a->N;
   VL_CHECK(n_valid % (16 * tpu) == 0, "vlaser_chain_gu: whole [gate|up] groups");
   ChainGuP p;
   p.h_in = (const bf16_t*)a->x; p.partials = a->partials; p.norm_w = (const bf16_t*)a->norm_w; p.h_out = (bf16_t*)a->h_out;
-  p.W = (const u32x4*)a->W; p.out = (bf16_t*)a->out;
+  p.W = (const u32x4*)a->W; p.out = (bf16_t*)a->out; p.w_scale = w8 ? a->w_scale : nullptr;
   p.M = a->M; p.ldo = a->ldo; p.n_valid = n_valid; p.eps = a->eps; p.inv_cpr = 8.0f / (float)a->K; p.dbg = a->dbg;
   const int units = a->N / (16 * tpu), longest = (units + 255) / 256, gx = (units + longest - 1) / longest;
   p.ulo = units / gx; p.urem = units % gx;
   const int ns = a->K / 256, cpt = (a->M * (a->K / 8) + 511) / 512;
   const int lds = ((a->M * (a->K * 2 + 16) + 15) & ~15) + longest * 8 * tpu * 64 * 16;
   hipStream_t stream = (hipStream_t)s;
-#define CG_CASE(NS_, UE_, SP_, CPT_, TPU_) if (ns == NS_ && longest == UE_ && a->n_partials == SP_ && cpt == CPT_ && tpu == TPU_) return chain_gu_launch<NS_, UE_, SP_, CPT_, TPU_>(p, gx, lds, stream);
-#define CG_CPT(NS_, UE_, SP_, TPU_) CG_CASE(NS_, UE_, SP_, 1, TPU_) CG_CASE(NS_, UE_, SP_, 2, TPU_) CG_CASE(NS_, UE_, SP_, 3, TPU_)
-  CG_VARIANTS(CG_CPT)
+#define CG_CASE(NS_, UE_, SP_, CPT_, TPU_, W8_) if (ns == NS_ && longest == UE_ && a->n_partials == SP_ && cpt == CPT_ && tpu == TPU_) return chain_gu_launch<NS_, UE_, SP_, CPT_, TPU_, W8_>(p, gx, lds, stream);
+#define CG_CPT(NS_, UE_, SP_, TPU_) CG_CASE(NS_, UE_, SP_, 1, TPU_, false) CG_CASE(NS_, UE_, SP_, 2, TPU_, false) CG_CASE(NS_, UE_, SP_, 3, TPU_, false)
+#define CG_W8_CPT(NS_, UE_, SP_, TPU_) CG_CASE(NS_, UE_, SP_, 1, TPU_, true) CG_CASE(NS_, UE_, SP_, 2, TPU_, true) CG_CASE(NS_, UE_, SP_, 3, TPU_, true)
+  if (w8) { CG_W8_VARIANTS(CG_W8_CPT) } else { CG_VARIANTS(CG_CPT) }
+#undef CG_W8_CPT
 #undef CG_CPT
 #undef CG_CASE
   vlaser_set_error("vlaser_chain_gu: no variant for K %d, %d units per workgroup, %d slabs, %d chunks per thread, %d tiles per unit", a->K, longest, a->n_partials, cpt, tpu);
   return -1;
 }
+extern "C" int vlaser_chain_gu(const VlaserSkinnyArgs* a, vl_stream_t s) { return chain_gu_entry(a, s, false); }
+extern "C" int vlaser_chain_gu_w8(const VlaserSkinnyArgs* a, vl_stream_t s) { return chain_gu_entry(a, s, true); }
 
 // ------------------------------------------------------------------------------------------------------------------ q / k / v
 struct ChainQkvP {
@@ -448,6 +493,7 @@ struct ChainDownP {
   const bf16_t* x; const u32x4* W; const bf16_t* res; bf16_t* h_out; float* out_f32;      // (out_f32: unread, kept so that the kernel arguments stay where the measured kernels fetch them)
   int M, N, ldx;
   unsigned long long* dbg;
+  const f32x4* w_scale;       // W8: fp32 [N / cols][4], the scales of a column group (the fourth repeats the third where cols = 3: ops.pack_down4_scales)
 };
 
 // A workgroup = CG groups of COLS (3 or 4) output columns over the WHOLE K = NW waves x NL loads x 128.  Lane (b = lane >> 2, i = lane & 3) of wave w, load l, group c
@@ -458,8 +504,12 @@ struct ChainDownP {
 // COLS = 3 puts N = 768 on 256 workgroups: a CU sustains ~35 GB/s of requests, so the launch lasts as long as the bytes of its busiest CU -- 54 KB of weights + the
 // whole [M, K] activation (every workgroup contracts over all of K: the price of publishing the result once) instead of 72 + 71 KB on 192 CUs.
 // RG = ceil(M / 4) row groups.
-template <int NW, int NL, int RG, int COLS, int CG, bool DBG>
+// W8: e4m3 codes (ops.pack_down4_e4m3): a lane's 16 bytes carry its 8 codes of load 2j, then its 8 codes of load 2j + 1 -- NL / 2 requests per group of the same
+// 16 x COLS x 16-byte shape, the same (column, k) elements in every lane, consumed in the same order.
+template <int NW, int NL, int RG, int COLS, int CG, bool DBG, bool W8 = false>
 __global__ __launch_bounds__(NW * 64) void chain_down_kernel(ChainDownP p) {
+  static_assert(NL % 2 == 0, "e4m3 weights: two loads per 16-byte request");
+  constexpr int NR = W8 ? NL / 2 : NL;         // weight requests per column group
   __shared__ __attribute__((aligned(16))) float part[NW][CG][RG][4][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = lane >> 2, i = lane & 3;
   const int M = p.M, n0 = blockIdx.x * (COLS * CG);
@@ -471,7 +521,9 @@ __global__ __launch_bounds__(NW * 64) void chain_down_kernel(ChainDownP p) {
   const bf16_t* rp = p.res + (size_t)fr_row * p.N + n0 + fr_cg * COLS;
 #pragma unroll
   for (int c = 0; c < COLS; ++c) rres[c] = bf16_to_f32(rp[c]);          // unconditional (clamped): no branch in front of the load burst
-  u32x4 xv[RG][NL], wv[CG][NL];
+  f32x4 wsc = {1.f, 1.f, 1.f, 1.f};
+  if constexpr (W8) wsc = p.w_scale[blockIdx.x * CG + fr_cg];
+  u32x4 xv[RG][NL], wv[CG][NR];
 #pragma unroll
   for (int rg = 0; rg < RG; ++rg) {
     const bf16_t* xr = p.x + (size_t)min(rg * 4 + i, M - 1) * p.ldx + (wave * NL) * 128 + b * 8;
@@ -480,9 +532,9 @@ __global__ __launch_bounds__(NW * 64) void chain_down_kernel(ChainDownP p) {
   }
   __builtin_amdgcn_sched_barrier(0);           // activations (L2) strictly in front of the weights (HBM) in the queue
   {
-    const u32x4* src = p.W + (((size_t)blockIdx.x * NW + wave) * NL) * (CG * 16 * COLS) + b * COLS + min(i, COLS - 1);
+    const u32x4* src = p.W + (((size_t)blockIdx.x * NW + wave) * NR) * (CG * 16 * COLS) + b * COLS + min(i, COLS - 1);
 #pragma unroll
-    for (int l = 0; l < NL; ++l)
+    for (int l = 0; l < NR; ++l)
 #pragma unroll
       for (int c = 0; c < CG; ++c) wv[c][l] = __builtin_nontemporal_load(src + (l * CG + c) * (16 * COLS));
   }
@@ -496,7 +548,9 @@ __global__ __launch_bounds__(NW * 64) void chain_down_kernel(ChainDownP p) {
   for (int l = 0; l < NL; ++l) {
 #pragma unroll
     for (int c = 0; c < CG; ++c) {
-      const s16x4 wlo = __builtin_bit_cast(s16x4, u32x2{wv[c][l][0], wv[c][l][1]}), whi = __builtin_bit_cast(s16x4, u32x2{wv[c][l][2], wv[c][l][3]});
+      u32x4 wb;
+      if constexpr (W8) wb = ch_e4m3x8(wv[c][l >> 1][2 * (l & 1)], wv[c][l >> 1][2 * (l & 1) + 1]); else wb = wv[c][l];
+      const s16x4 wlo = __builtin_bit_cast(s16x4, u32x2{wb[0], wb[1]}), whi = __builtin_bit_cast(s16x4, u32x2{wb[2], wb[3]});
 #pragma unroll
       for (int rg = 0; rg < RG; ++rg) {
         const s16x4 xlo = __builtin_bit_cast(s16x4, u32x2{xv[rg][l][0], xv[rg][l][1]}), xhi = __builtin_bit_cast(s16x4, u32x2{xv[rg][l][2], xv[rg][l][3]});
@@ -529,7 +583,7 @@ __global__ __launch_bounds__(NW * 64) void chain_down_kernel(ChainDownP p) {
     }
     bf16_t* op = p.h_out + (size_t)fr_row * p.N + n0 + fr_cg * COLS;
 #pragma unroll
-    for (int c = 0; c < COLS; ++c) op[c] = f32_to_bf16(s4[c] + rres[c]);
+    for (int c = 0; c < COLS; ++c) op[c] = f32_to_bf16((W8 ? s4[c] * wsc[c] : s4[c]) + rres[c]);       // the column's scale on the reduced fp32 sum, before the first rounding
   }
   CH_STAMP(5);
 }
@@ -541,6 +595,7 @@ extern "C" int vlaser_chain_down_supported(int M, int N, int K) {
   vlaser_chain_down_geometry(N, &c, &g);
   return g == 1 || M <= 8;            // two column groups per workgroup x 16 rows would spill
 }
+extern "C" int vlaser_chain_down_w8_supported(int M, int N, int K) { return vlaser_chain_down_supported(M, N, K); }      // every case of the one dispatch below, in both formats
 /* column geometry of vlaser_chain_down / ops.pack_down4 for an output width N: cols per group (3 or 4) and groups per workgroup, chosen for ~256 workgroups */
 extern "C" int vlaser_chain_down_geometry(int N, int* cols, int* groups) {
   const int c = (N % 3 == 0) ? 3 : 4;
@@ -550,23 +605,15 @@ extern "C" int vlaser_chain_down_geometry(int N, int* cols, int* groups) {
   return N / (c * g);
 }
 
-/* x bf16 [M, ldx] (ldx >= K), W = ops.pack_down4(down_proj.weight), res / h_out bf16 [M, N] (may not alias): h_out = bf16(res + x @ W^T) */
-extern "C" int vlaser_chain_down(const void* x, int ldx, const void* W, const void* res, void* h_out, int M, int N, int K, unsigned long long* dbg, vl_stream_t s) {
-  VL_CHECK(x && W && res && h_out && res != h_out, "vlaser_chain_down: null operand (or res == h_out: every workgroup reads its residual columns while others store)");
-  VL_CHECK(vlaser_chain_down_supported(M, N, K) && ldx >= K && ldx % 8 == 0, "vlaser_chain_down: built for K = 8960 (7 waves x 10 loads x 128), N %% 3 == 0 or N %% 4 == 0, M <= 16 (got M %d N %d K %d)", M, N, K);
-  VL_CHECK(((uintptr_t)W & 15) == 0 && ((uintptr_t)x & 15) == 0, "vlaser_chain_down: alignment");
-  ChainDownP p;
-  p.x = (const bf16_t*)x; p.W = (const u32x4*)W; p.res = (const bf16_t*)res; p.h_out = (bf16_t*)h_out; p.out_f32 = nullptr; p.M = M; p.N = N; p.ldx = ldx; p.dbg = dbg;
-  int cols, groups;
-  const int wgs = vlaser_chain_down_geometry(N, &cols, &groups);
-  const int rg = (M + 3) / 4;
-  hipStream_t stream = (hipStream_t)s;
-#define CD_LAUNCH(RG_, COLS_, CG_)                                                                                                       \
-  do {                                                                                                                                   \
-    if (dbg) hipLaunchKernelGGL((chain_down_kernel<7, 10, RG_, COLS_, CG_, true>), dim3(wgs), dim3(7 * 64), 0, stream, p);                 \
-    else hipLaunchKernelGGL((chain_down_kernel<7, 10, RG_, COLS_, CG_, false>), dim3(wgs), dim3(7 * 64), 0, stream, p);                    \
-    VL_LAUNCH_CHECK();                                                                                                                   \
-    return 0;                                                                                                                            \
+template <bool W8>
+static int chain_down_dispatch(const ChainDownP& p, int wgs, int cols, int groups, hipStream_t stream) {
+  const int rg = (p.M + 3) / 4;
+#define CD_LAUNCH(RG_, COLS_, CG_)                                                                                                         \
+  do {                                                                                                                                     \
+    if (p.dbg) hipLaunchKernelGGL((chain_down_kernel<7, 10, RG_, COLS_, CG_, true, W8>), dim3(wgs), dim3(7 * 64), 0, stream, p);             \
+    else hipLaunchKernelGGL((chain_down_kernel<7, 10, RG_, COLS_, CG_, false, W8>), dim3(wgs), dim3(7 * 64), 0, stream, p);                  \
+    VL_LAUNCH_CHECK();                                                                                                                     \
+    return 0;                                                                                                                              \
   } while (0)
 #define CD_CASE1(RG_) if (rg == RG_ && groups == 1) { if (cols == 3) CD_LAUNCH(RG_, 3, 1); else CD_LAUNCH(RG_, 4, 1); }
 #define CD_CASE2(RG_) if (rg == RG_ && groups == 2) { if (cols == 3) CD_LAUNCH(RG_, 3, 2); else CD_LAUNCH(RG_, 4, 2); }
@@ -576,6 +623,27 @@ extern "C" int vlaser_chain_down(const void* x, int ldx, const void* W, const vo
 #undef CD_LAUNCH
   vlaser_set_error("vlaser_chain_down: no variant");
   return -1;
+}
+
+/* x bf16 [M, ldx] (ldx >= K), W = ops.pack_down4(down_proj.weight), res / h_out bf16 [M, N] (may not alias): h_out = bf16(res + x @ W^T).
+   w8: W = ops.pack_down4_e4m3(codes), w_scale = ops.pack_down4_scales(scale): h_out = bf16(res + scale * (x @ codes^T)) */
+static int chain_down_entry(const void* x, int ldx, const void* W, const float* w_scale, const void* res, void* h_out, int M, int N, int K, unsigned long long* dbg, vl_stream_t s, bool w8) {
+  VL_CHECK(x && W && res && h_out && res != h_out, "vlaser_chain_down: null operand (or res == h_out: every workgroup reads its residual columns while others store)");
+  VL_CHECK(!w8 || w_scale, "vlaser_chain_down_w8: null w_scale (fp32 column scales of the e4m3 weights, ops.pack_down4_scales)");
+  VL_CHECK(vlaser_chain_down_supported(M, N, K) && ldx >= K && ldx % 8 == 0, "vlaser_chain_down: built for K = 8960 (7 waves x 10 loads x 128), N %% 3 == 0 or N %% 4 == 0, M <= 16 (got M %d N %d K %d)", M, N, K);
+  VL_CHECK(((uintptr_t)W & 15) == 0 && ((uintptr_t)x & 15) == 0 && (!w8 || ((uintptr_t)w_scale & 15) == 0), "vlaser_chain_down: alignment");
+  ChainDownP p;
+  p.x = (const bf16_t*)x; p.W = (const u32x4*)W; p.res = (const bf16_t*)res; p.h_out = (bf16_t*)h_out; p.out_f32 = nullptr; p.M = M; p.N = N; p.ldx = ldx; p.dbg = dbg;
+  p.w_scale = w8 ? (const f32x4*)w_scale : nullptr;
+  int cols, groups;
+  const int wgs = vlaser_chain_down_geometry(N, &cols, &groups);
+  return w8 ? chain_down_dispatch<true>(p, wgs, cols, groups, (hipStream_t)s) : chain_down_dispatch<false>(p, wgs, cols, groups, (hipStream_t)s);
+}
+extern "C" int vlaser_chain_down(const void* x, int ldx, const void* W, const void* res, void* h_out, int M, int N, int K, unsigned long long* dbg, vl_stream_t s) {
+  return chain_down_entry(x, ldx, W, nullptr, res, h_out, M, N, K, dbg, s, false);
+}
+extern "C" int vlaser_chain_down_w8(const void* x, int ldx, const void* W, const float* w_scale, const void* res, void* h_out, int M, int N, int K, unsigned long long* dbg, vl_stream_t s) {
+  return chain_down_entry(x, ldx, W, w_scale, res, h_out, M, N, K, dbg, s, true);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ attention over the KV cache, <= 16 query tokens

@@ -34,8 +34,21 @@ class QwenLayerWeights:
                                        g('self_attn.v_proj.weight'), g('self_attn.q_proj.bias'),
                                        g('self_attn.k_proj.bias'), g('self_attn.v_proj.bias'), llm.head_dim)
         wo = g('self_attn.o_proj.weight')
-        wgu = ops.pack_gate_up(g('mlp.gate_proj.weight'), g('mlp.up_proj.weight'))
-        wdown = g('mlp.down_proj.weight')
+        mlp8 = 'mlp8' in opts
+        if mlp8:
+            # 'mlp8': the MLP weights as e4m3 codes + power-of-two row scales (ops.quantize_rows_e4m3, on the host at load), in the packings of the W8 chain kernels; the
+            # bf16 packings below are read only by the launches those replace and are not built
+            H, I = llm.hidden_size, llm.intermediate_size
+            if gemm or not skinny or 'gu16' not in opts or not chain_packed(opts, H, I):
+                raise ValueError("'mlp8' serves the weight-streaming chain path only: needs 'chain', 'qkv16', 'gu16' and hidden 768 / MLP width 8960")
+            q = lambda k: ops.quantize_rows_e4m3(sd[p + k])
+            self.gu8 = ops.pack_gate_up8_e4m3(*q('mlp.gate_proj.weight'), *q('mlp.up_proj.weight')).to(device)
+            dc, ds = q('mlp.down_proj.weight')
+            self.down8, self.down8_scale = ops.pack_down4_e4m3(dc).to(device), ops.pack_down4_scales(ds).to(device)
+            self.sk_gu = self.sk_down = None
+        else:
+            wgu = ops.pack_gate_up(g('mlp.gate_proj.weight'), g('mlp.up_proj.weight'))
+            wdown = g('mlp.down_proj.weight')
         self.ln_in = g('input_layernorm.weight')
         self.ln_post = g('post_attention_layernorm.weight')
         if gemm:
@@ -50,17 +63,18 @@ class QwenLayerWeights:
             else:
                 self.sk_qkv = ops.pack_skinny(wqkv, 1)
             self.sk_o = ops.pack_skinny(wo, ks_o, tpu_o)
-            # wide output + short K (action expert: 17920 x 768): 96-row units (tpu = 6) measured slower on MI355X (12.3 vs 11.2 us) and left
-            # the kernel in r05; 16-row lane-local units ('gu16', r03) balance 1120 units over 256 workgroups (80 vs 96 rows on the longest)
-            if 'gu16' in opts:
-                self.sk_gu = ops.pack_skinny(ops.pack_gate_up8(g('mlp.gate_proj.weight'), g('mlp.up_proj.weight')), 1, 1)
-            else:
-                self.sk_gu = ops.pack_skinny(wgu, 1, 2)
-            self.sk_down = ops.pack_skinny(wdown, ks_down, tpu_down, k_pad=i_pad)
-            # 'chain' (r05, csrc/chain.hip): the down projection without cross-workgroup split-K (4 output columns per workgroup over the whole K) publishes the next
-            # layer's residual stream as bf16
-            if chain_packed(opts, wdown.shape[0], wdown.shape[1]):
-                self.sk_down4 = ops.pack_down4(wdown)
+            if not mlp8:
+                # wide output + short K (action expert: 17920 x 768): 96-row units (tpu = 6) measured slower on MI355X (12.3 vs 11.2 us) and left
+                # the kernel in r05; 16-row lane-local units ('gu16', r03) balance 1120 units over 256 workgroups (80 vs 96 rows on the longest)
+                if 'gu16' in opts:
+                    self.sk_gu = ops.pack_skinny(ops.pack_gate_up8(g('mlp.gate_proj.weight'), g('mlp.up_proj.weight')), 1, 1)
+                else:
+                    self.sk_gu = ops.pack_skinny(wgu, 1, 2)
+                self.sk_down = ops.pack_skinny(wdown, ks_down, tpu_down, k_pad=i_pad)
+                # 'chain' (r05, csrc/chain.hip): the down projection without cross-workgroup split-K (4 output columns per workgroup over the whole K) publishes the next
+                # layer's residual stream as bf16
+                if chain_packed(opts, wdown.shape[0], wdown.shape[1]):
+                    self.sk_down4 = ops.pack_down4(wdown)
 
 
 def chain_packed(opts, H, I):
@@ -92,21 +106,28 @@ def path_geometry(llm: LLMConfig, opts):
     H, I, nq, nkv, hd = llm.hidden_size, llm.intermediate_size, llm.num_attention_heads, llm.num_key_value_heads, llm.head_dim
     tpu_o, ks_o = stack_geometry(llm)[:2]
     tpu_gu = 1 if 'gu16' in opts else 2
-    return dict(chain_packed=chain_packed(opts, H, I), H=H, I=I, n_qkv=ops.skinny_rows((nq + 2 * nkv) * hd, 1 if 'qkv16' in opts else 2),
+    return dict(chain_packed=chain_packed(opts, H, I), mlp8='mlp8' in opts, H=H, I=I, n_qkv=ops.skinny_rows((nq + 2 * nkv) * hd, 1 if 'qkv16' in opts else 2),
                 n_gu=ops.skinny_rows(2 * I, tpu_gu), tpu_gu=tpu_gu, n_o=ops.skinny_rows(H, tpu_o), tpu_o=tpu_o, ks_o=ks_o, nq=nq, nkv=nkv, hd=hd)
 
 
 def layer_path(*, chain_packed, H, I, n_qkv, n_gu, tpu_gu, n_o, tpu_o, ks_o, nq, nkv, hd, act_width, M, tok_per_batch, kv_len, n_partials=0, input_is_hB=False,
-               skip_post_attn=False, dense_mask=False):
+               skip_post_attn=False, dense_mask=False, mlp8=False):
     """(chain, chain_ao) of one skinny_layer call -- the ONE place that decides between the kernels of csrc/chain.hip and of csrc/skinny.hip (and the only caller of
     the library's *_supported predicates).  Integers and booleans in (path_geometry of the stack + the call), no tensors.
     chain: q/k/v, gate/up and down on the latency-built kernels -- the layer takes a residual stream that is already reduced (n_partials == 0: the action encoder's output,
     or what the previous layer's vlaser_chain_down published; not hB, which this layer's gate/up launch overwrites while its other workgroups still read their input) and hands
     on (hC, None, 0).
     chain_ao: attention + o_proj on the one-wave-per-split attention / bf16-partial merge pair, when the key count gives a split count they are built for.
-    A dense additive mask (ABI 8) is served by the chain attention only (every <= 16-row launch of the VLA at its shipped widths): NotImplementedError elsewhere."""
-    chain = (chain_packed and act_width == I and n_partials == 0 and not input_is_hB
-             and ops.chain_qkv_supported(M, n_qkv, H) and ops.chain_gu_supported(M, n_gu, H, ks_o, tpu_gu) and ops.chain_down_supported(M, H, I))
+    A dense additive mask (ABI 8) is served by the chain attention only (every <= 16-row launch of the VLA at its shipped widths): NotImplementedError elsewhere.
+    mlp8: the stack holds its MLP weights as e4m3 codes, which only the W8 forms of the chain gate/up and down kernels read: chain means those two launches, and a call
+    that would run the MLP off the chain path raises NotImplementedError (a call that stops after q/k/v reads no MLP weight)."""
+    if mlp8:
+        mlp_ok = ops.chain_gu_w8_supported(M, n_gu, H, ks_o, tpu_gu) and ops.chain_down_w8_supported(M, H, I)
+    else:
+        mlp_ok = ops.chain_gu_supported(M, n_gu, H, ks_o, tpu_gu) and ops.chain_down_supported(M, H, I)
+    chain = chain_packed and act_width == I and n_partials == 0 and not input_is_hB and ops.chain_qkv_supported(M, n_qkv, H) and mlp_ok
+    if mlp8 and not chain and not skip_post_attn:
+        raise NotImplementedError("'mlp8' (e4m3 MLP weights) needs the chain path: hidden 768, MLP width 8960, <= 16 rows, an already reduced residual stream")
     chain_ao = (chain and not skip_post_attn and tpu_o == 1 and tok_per_batch * (nq // nkv) <= 32
                 and ops.chain_oproj_supported(M, n_o, nq * hd, ks_o, ops.chain_attn_splits(kv_len), nq // nkv))
     if dense_mask and not (chain_ao or (chain and skip_post_attn)):
@@ -130,7 +151,8 @@ class QwenStack:
         self.sk_head = ops.pack_skinny(self.head, 1) if (self.head is not None and skinny) else None
         self.path = p = path_geometry(llm, self.opts)
         for lw in self.layers if skinny else ():
-            assert (lw.sk_qkv.N, lw.sk_gu.N, lw.sk_gu.tpu, lw.sk_o.N, lw.sk_o.tpu, lw.sk_down4 is not None) == \
+            gu = lw.gu8 if p['mlp8'] else lw.sk_gu
+            assert (lw.sk_qkv.N, gu.N, gu.tpu, lw.sk_o.N, lw.sk_o.tpu, (lw.down8 if p['mlp8'] else lw.sk_down4) is not None) == \
                 (p['n_qkv'], p['n_gu'], p['tpu_gu'], p['n_o'], p['tpu_o'], p['chain_packed']), 'path_geometry disagrees with the packed weights'
 
     @property
@@ -381,6 +403,10 @@ def skinny_layer(stack: QwenStack, lw: QwenLayerWeights, sb: SkinnyBuffers, h_in
     return plan.result
 
 
+def _chain_down_w8(sb, lw, M, H, I, down, stream):
+    ops.chain_down_w8(sb.act, lw.down8, lw.down8_scale, sb.hB, sb.hC, M, H, I, dbg=down.dbg, stream=stream)
+
+
 def _chain_down(sb, W4, M, H, I, down, stream):          # `down.dbg`: read at launch time, tools set it after the plan is built
     ops.chain_down(sb.act, W4, sb.hB, sb.hC, M, H, I, dbg=down.dbg, stream=stream)
 
@@ -422,11 +448,15 @@ def _build_plan(stack, lw, sb, h_in, partials, n_partials, cache, layer, rope, p
         plan.o = ops.skinny_args(None, lw.sk_o, M, out_f32=sb.part_o, attn_m=sb.attn_parts[0], attn_l=sb.attn_parts[1],
                                  attn_o=sb.attn_parts[2], attn_splits=1, attn_group=nq // nkv, attn_nq=tok_per_batch)
         plan.launches += [('attn', ops.launch_attn_skinny, (plan.attn,)), ('o', ops.launch_skinny, (L.PRO_ATTN, L.SK_PARTIAL, plan.o[0]))]
-    plan.gu = ops.skinny_args(h_in if chain else sb.hA, lw.sk_gu, M, partials=sb.part_o, n_partials=stack.ks_o, norm_w=lw.ln_post,
+    mlp8 = stack.path['mlp8']          # (layer_path has raised if the MLP of an 'mlp8' stack would leave the chain path)
+    plan.gu = ops.skinny_args(h_in if chain else sb.hA, lw.gu8 if mlp8 else lw.sk_gu, M, partials=sb.part_o, n_partials=stack.ks_o, norm_w=lw.ln_post,
                               eps=llm.rms_norm_eps, h_out=sb.hB, out=sb.act, ldo=sb.act.shape[1])
     if chain:
         plan.down = SimpleNamespace(dbg=None)
-        plan.launches += [('gu', ops.launch_chain_gu, (plan.gu[0],)), ('down', _chain_down, (sb, lw.sk_down4, M, H, I, plan.down))]
+        if mlp8:
+            plan.launches += [('gu', ops.launch_chain_gu_w8, (plan.gu[0],)), ('down', _chain_down_w8, (sb, lw, M, H, I, plan.down))]
+        else:
+            plan.launches += [('gu', ops.launch_chain_gu, (plan.gu[0],)), ('down', _chain_down, (sb, lw.sk_down4, M, H, I, plan.down))]
         plan.result = (sb.hC, None, 0)
     else:
         plan.down = ops.skinny_args(sb.act, lw.sk_down, M, out_f32=sb.part_d)

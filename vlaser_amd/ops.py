@@ -275,10 +275,14 @@ def attn_partial_buffers(batch, n_kv, device, max_splits=8):
 # ------------------------------------------------------------------------------------------------ skinny GEMV
 class PackedW:
     """Weight [N,K] packed for the skinny kernel: fragment-major [k_splits][N/32][8 waves][steps][2 tiles][64 lanes][8]."""
-    __slots__ = ('t', 'N', 'n_valid', 'K', 'k_splits', 'tpu')
+    __slots__ = ('t', 'N', 'n_valid', 'K', 'k_splits', 'tpu', 'scale')
 
-    def __init__(self, t, N, n_valid, K, k_splits, tpu=2):
+    def __init__(self, t, N, n_valid, K, k_splits, tpu=2, scale=None):
         self.t, self.N, self.n_valid, self.K, self.k_splits, self.tpu = t, N, n_valid, K, k_splits, tpu
+        self.scale = scale          # e4m3 packings (pack_gate_up8_e4m3): fp32 [N] row scales in packed row order; None for bf16 weights
+
+    def to(self, device):
+        return PackedW(self.t.to(device), self.N, self.n_valid, self.K, self.k_splits, self.tpu, None if self.scale is None else self.scale.to(device))
 
 
 SK_WAVES = 8
@@ -316,6 +320,8 @@ def skinny_args(x, W: PackedW, M, **kw):
     a.x, a.W = _p(x), W.t.data_ptr()
     a.M, a.N, a.K, a.ldw, a.n_valid, a.tiles_per_unit = M, W.N, W.K, W.K, W.n_valid, W.tpu
     a.k_splits = W.k_splits
+    if W.scale is not None:
+        a.w_scale = W.scale.data_ptr()
     a.eps = kw.pop('eps', 1e-6)
     keep = None
     b = kw.get('bias')
@@ -354,6 +360,114 @@ def pack_down4(W, nw=DOWN4_WAVES, nl=DOWN4_LOADS):
     assert N == wgs * cols * groups and K == nw * nl * 128, (N, K)
     v = W.view(wgs, groups, cols, nw, nl, 16, 8)                           # [wg, c, i, w, l, b, e]
     return v.permute(0, 3, 4, 1, 5, 2, 6).contiguous().reshape(-1)         # [wg, w, l, c, b, i, e]
+
+
+# ---- one-byte MLP weights of the action expert (option 'mlp8'; csrc/chain.hip W8 forms): OCP e4m3 codes + one power-of-two fp32 scale per weight row
+E4M3_MAX = 448.0
+GU8_WAVE_BYTES = 64 * 16 + 64 * 8          # a wave's share of a 16-row unit at K = 768: the lanes' K-steps 0 and 1 (16 bytes each), then K-step 2 (8 bytes each)
+
+
+def quantize_rows_e4m3(w):
+    """w [N, K] (any float dtype, rounded to bf16 first as the engine does) -> (codes uint8 [N, K], scale fp32 [N]) with w ~= scale[:, None] * e4m3(codes):
+    scale[n] = 2^ceil(log2(absmax_n / 448)) (1 for a zero row), codes = round-to-nearest-even of w / scale in OCP e4m3 (torch.float8_e4m3fn).  The scale is a power of
+    two, so the quantisation loses no relative precision to it, every dequantised value is exact in bf16 (<= 4 significant bits) and scaling an fp32 sum by it is
+    exact -- what makes the W8 kernels testable bit for bit.  |w / scale| <= 448, so neither NaN code (0x7F, 0xFF) is ever produced.  Plain torch on the CPU."""
+    assert w.dim() == 2 and w.is_floating_point()
+    wf = w.detach().to('cpu').to(BF16).to(torch.float64)
+    assert bool(torch.isfinite(wf).all()), 'quantize_rows_e4m3: non-finite weight'
+    amax = wf.abs().amax(dim=1)
+    m, e = torch.frexp(amax / E4M3_MAX)                       # amax / 448 = m 2^e, m in [0.5, 1): ceil(log2) = e, or e - 1 at an exact power of two
+    e = torch.where(m == 0.5, e - 1, e)
+    scale = torch.where(amax > 0, torch.ldexp(torch.ones_like(amax), e), torch.ones_like(amax))
+    codes = (wf / scale[:, None]).to(torch.float32).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes.contiguous(), scale.to(torch.float32)
+
+
+def dequantize_rows_e4m3(codes, scale):
+    """The bf16 tensor [N, K] that (codes, scale) stand for (exact for power-of-two scales)."""
+    return (codes.view(torch.float8_e4m3fn).to(torch.float32) * scale.to(codes.device)[:, None].to(torch.float32)).to(BF16)
+
+
+def unpack_gate_up8(rows):
+    """Inverse of pack_gate_up8 on its [2I, ...] row order -> (gate rows, up rows)."""
+    n = rows.shape[0]
+    v = rows.reshape(n // 16, 4, 4, *rows.shape[1:])            # [unit, lane group, (g0, g1, u0, u1), ...]
+    return v[:, :, :2].reshape(n // 2, *rows.shape[1:]).contiguous(), v[:, :, 2:].reshape(n // 2, *rows.shape[1:]).contiguous()
+
+
+def pack_gate_up8_e4m3(gate_codes, gate_scale, up_codes, up_scale):
+    """e4m3 gate / up codes [I, 768] + row scales -> PackedW (tpu = 1, .scale = fp32 [2I] in packed row order) for vlaser_chain_gu_w8.  Rows as pack_gate_up8; lane
+    (r = l & 15, g = l >> 4) of wave w, unit u receives the same 3 x 8 elements W[16u + r, 96w + 32s + 8g : + 8], s = 0, 1, 2 as from pack_skinny(..., 1, 1), in 24 bytes:
+    K = 768 gives a wave an ODD number of K-steps, so a unit's share of a wave is 64 x 16 bytes (K-steps 0 and 1 of each lane: one 16-byte load) followed by 64 x 8 bytes
+    (K-step 2: one 8-byte load) -- 1536 contiguous bytes, two requests per unit where the bf16 form issues three."""
+    rows = pack_gate_up8(gate_codes, up_codes)
+    N, K = rows.shape
+    assert rows.dtype == torch.uint8 and K == 3 * 32 * SK_WAVES and N % 16 == 0, (rows.dtype, N, K)
+    v = rows.view(N // 16, 16, SK_WAVES, 3, 4, 8)                               # [u, r, w, s, g, e]
+    a = v[:, :, :, :2].permute(0, 2, 4, 1, 3, 5).reshape(N // 16, SK_WAVES, 1024)     # [u, w, g, r, s, e]
+    b = v[:, :, :, 2].permute(0, 2, 3, 1, 4).reshape(N // 16, SK_WAVES, 512)          # [u, w, g, r, e]
+    scale = pack_gate_up8(gate_scale.reshape(-1, 1), up_scale.reshape(-1, 1)).reshape(-1).to(torch.float32)
+    return PackedW(torch.cat([a, b], dim=2).reshape(-1).contiguous(), N, N, K, 1, 1, scale=scale.contiguous())
+
+
+def unpack_gate_up8_e4m3(W: PackedW):
+    """Inverse of pack_gate_up8_e4m3 -> (gate_codes, gate_scale, up_codes, up_scale)."""
+    U = W.N // 16
+    t = W.t.view(U, SK_WAVES, GU8_WAVE_BYTES)
+    a = t[:, :, :1024].reshape(U, SK_WAVES, 4, 16, 2, 8).permute(0, 3, 1, 4, 2, 5)      # [u, w, g, r, s, e] -> [u, r, w, s, g, e]
+    b = t[:, :, 1024:].reshape(U, SK_WAVES, 4, 16, 1, 8).permute(0, 3, 1, 4, 2, 5)
+    gc, uc = unpack_gate_up8(torch.cat([a, b], dim=3).reshape(W.N, W.K))
+    gs, us = unpack_gate_up8(W.scale.reshape(-1, 1))
+    return gc, gs.reshape(-1), uc, us.reshape(-1)
+
+
+def pack_down4_e4m3(codes, nw=DOWN4_WAVES, nl=DOWN4_LOADS):
+    """e4m3 down_proj codes [N, K] -> [workgroup][nw waves][nl / 2 load pairs][groups][16 blocks][cols][2 loads][8] bytes for vlaser_chain_down_w8: the 16 bytes of block b,
+    column i hold W[.., (w nl + 2j) 128 + 8b : + 8] then W[.., (w nl + 2j + 1) 128 + 8b : + 8] -- the lane's elements of loads 2j and 2j + 1 of pack_down4, in that order."""
+    N, K = codes.shape
+    wgs, cols, groups = chain_down_geometry(N)
+    assert codes.dtype == torch.uint8 and N == wgs * cols * groups and K == nw * nl * 128 and nl % 2 == 0, (codes.dtype, N, K)
+    v = codes.view(wgs, groups, cols, nw, nl // 2, 2, 16, 8)                    # [wg, c, i, w, j, l2, b, e]
+    return v.permute(0, 3, 4, 1, 6, 2, 5, 7).contiguous().reshape(-1)           # [wg, w, j, c, b, i, l2, e]
+
+
+def unpack_down4_e4m3(t, N, nw=DOWN4_WAVES, nl=DOWN4_LOADS):
+    wgs, cols, groups = chain_down_geometry(N)
+    v = t.view(wgs, nw, nl // 2, groups, 16, cols, 2, 8)
+    return v.permute(0, 3, 5, 1, 2, 6, 4, 7).contiguous().reshape(N, nw * nl * 128)
+
+
+def pack_down4_scales(scale):
+    """fp32 [N] column scales -> [N / cols][4]: one 16-byte load per column group (the fourth entry repeats the third where cols = 3, as the fourth lane of a block
+    re-reads the third's weights)."""
+    _, cols, _ = chain_down_geometry(scale.numel())
+    v = scale.to(torch.float32).view(-1, cols)
+    return torch.cat([v, v[:, -1:].expand(-1, 4 - cols)], dim=1).contiguous()
+
+
+def unpack_down4_scales(packed, N):
+    _, cols, _ = chain_down_geometry(N)
+    return packed[:, :cols].reshape(-1).contiguous()
+
+
+def chain_gu_w8_supported(M, N, K, n_partials, tpu=1):
+    return bool(L.lib().vlaser_chain_gu_w8_supported(M, N, K, n_partials, tpu))
+
+
+def chain_down_w8_supported(M, N, K):
+    return bool(L.lib().vlaser_chain_down_w8_supported(M, N, K))
+
+
+def launch_chain_gu_w8(a, stream=None):
+    L.check(L.lib().vlaser_chain_gu_w8(C.byref(a), _stream() if stream is None else stream), 'vlaser_chain_gu_w8')
+
+
+def chain_down_w8(x, W8, scale4, res, h_out, M, N, K, dbg=None, stream=None):
+    """h_out[M, N] = bf16(res + scale * (x[M, :K] @ codes^T)), W8 = pack_down4_e4m3(codes), scale4 = pack_down4_scales(scale)."""
+    assert x.dtype == BF16 and res.dtype == BF16 and h_out.dtype == BF16 and x.stride(-1) == 1 and res.data_ptr() != h_out.data_ptr()
+    assert W8.dtype == torch.uint8 and scale4.dtype == torch.float32 and scale4.is_contiguous()
+    L.check(L.lib().vlaser_chain_down_w8(x.data_ptr(), x.stride(0), W8.data_ptr(), scale4.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K,
+                                         dbg if isinstance(dbg, int) else _p(dbg), _stream() if stream is None else stream), 'vlaser_chain_down_w8')
 
 
 def chain_qkv_supported(M, N, K):

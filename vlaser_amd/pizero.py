@@ -147,6 +147,11 @@ class PiZero:
     #   chain (r05, needs qkv16): q/k/v, gate/up and the down projection on the latency-built kernels of csrc/chain.hip -- every request of a launch issued up front,
     #          one wave per q/k/v unit, the down projection publishing the bf16 residual stream once (no split-K slabs for the next layer to re-reduce): ON.  Same
     #          tolerance against oracle / goldens as the skinny kernels; gate/up bit-identical, q/k/v and down sum in a different fp32 order
+    #   mlp8 (opt-in, needs chain + qkv16 + gu16; also expert_mlp_weights='fp8'): the expert's gate/up/down weights stored as OCP e4m3 codes with one power-of-two
+    #          scale per row, quantised at load (ops.quantize_rows_e4m3) and streamed by the W8 forms of the chain gate/up and down kernels -- half the MLP's bytes and
+    #          footprint (1.16 -> 0.58 GB at full depth).  Weight-only: bf16 MFMAs and summation orders unchanged, so the chunk is bit-identical to the default path run
+    #          on the dequantised weights.  It is NOT the bf16 model: on the synthetic test model the chunk moves by 1.5e-2 (the reference's own bf16 mode sits 6.5e-3 to
+    #          1.6e-2 from its fp32 chunk); the deviation on released checkpoints is unmeasured.  A/B: profiles/fp8_mlp_ab.md.  OFF by default
     EULER_DEFAULT = 'qkv16,gu16,glue1,chain'      # (gu16 ON with chain since r05: 224 workgroups x 5 units instead of 187 x 3, 11.79 -> 11.68 ms per chunk, same-box A/B)
 
     ERR_BITS = {1: 'image_text_proprio_mask: the keys the proprio row sees are not a contiguous valid prefix',
@@ -156,7 +161,7 @@ class PiZero:
                    'the proprio token\'s K / V exist'}
 
     def __init__(self, cfg: VLAConfig, device='cuda', max_batch=1, use_graph=True, ride_proprio=True, naive_support=False, euler_opts=None, output_ring=0,
-                 general_masks=False):
+                 general_masks=False, expert_mlp_weights='bf16'):
         L.lib()
         if not torch.cuda.is_available():
             raise L.VlaserHipError('vlaser_amd needs an MI355X (gfx950) GPU: there is no CPU fallback')
@@ -184,6 +189,16 @@ class PiZero:
         self.general_masks = bool(general_masks)
         eo = os.environ.get('VLASER_EULER', self.EULER_DEFAULT) if euler_opts is None else euler_opts
         self.euler_opts = tuple(x for x in eo.split(',') if x and x != 'none')
+        # expert_mlp_weights='fp8' (opt-in; the same as 'mlp8' among the Euler options): see 'mlp8' above -- not the bf16 model, deviation on released checkpoints unmeasured
+        if expert_mlp_weights not in ('bf16', 'fp8'):
+            raise ValueError(f"expert_mlp_weights: 'bf16' or 'fp8', not {expert_mlp_weights!r}")
+        if expert_mlp_weights == 'fp8' and 'mlp8' not in self.euler_opts:
+            self.euler_opts += ('mlp8',)
+        if 'mlp8' in self.euler_opts:
+            missing = [o for o in ('chain', 'qkv16', 'gu16') if o not in self.euler_opts]
+            if missing:
+                raise ValueError(f"Euler option 'mlp8' (expert_mlp_weights='fp8') needs {', '.join(missing)}: the e4m3 MLP weights are read by the chain kernels' 16-row-unit forms only")
+        self.expert_mlp_weights = 'fp8' if 'mlp8' in self.euler_opts else 'bf16'
         self._graphs = {}
         self._pos_state = None
         self._pos_next = None
