@@ -348,6 +348,10 @@ int vlaser_argmax(const float* logits, int M, int N, int64_t* out_id, const void
 /* pi0 head glue: SinusoidalPosEmb + ActionEncoder.linear_1 (modules.py:9-22,45-50); proprio_encoder
  * (pizero_internvl.py:823); final norm + action_decoder + Euler update (+clamp) (pizero_internvl.py:911-932). */
 int vlaser_vla_prep(const float* action, const void* w1, const void* b1, void* xcat, int M, int W, int adim, float t, float max_period, vl_stream_t stream);
+/* vlaser_vla_prep with one flow-matching time per sample: t = device float[ceil(M / rows_per_t)], row m uses t[m / rows_per_t] (`PiZero.forward` at batch B embeds
+ * t [B] and repeats it over the action tokens, pizero_internvl.py:1064-1197 with modules.py:9-22,45-50).  Per row bit-identical to vlaser_vla_prep with that scalar. */
+int vlaser_vla_prep_rows(const float* action, const void* w1, const void* b1, void* xcat, int M, int W, int adim, const float* t, int rows_per_t, float max_period,
+                         vl_stream_t stream);
 int vlaser_small_linear(const float* x, const void* w, const void* b, void* out, int M, int N, int K, vl_stream_t stream);
 /* (ABI 5) ring (nullable): the updated actions are ALSO written to slot (ring_ctr[0] mod ring_n) of `ring` (ring_stride floats per slot), so that the host
  * surface can hand out a view of the result instead of launching a copy (the reference returns a fresh tensor: pizero_internvl.py:934-936).
@@ -528,6 +532,14 @@ int vlaser_silu_bwd(const void* x, const void* dy, void* dx, long long n, vl_str
 int vlaser_attn_rows_bwd_ws_floats(int n_q);
 int vlaser_attn_rows_bwd(const void* q, const void* K, const void* VT, const void* dO, const void* O, void* dq, void* dk, void* dv, int R, int n_q,
                          int n_kv, int s_max, int valid_len, int blk_start, int first_tok_self, float scale, float* ws, vl_stream_t stream);
+/* vlaser_attn_rows_bwd for the expert rows of B samples in one call (two launches): the backward of `PiZero.forward`'s joint attention at batch B (pizero_internvl.py:1064-1197,
+ * joint_model.py:410-696) restricted to the proprio + action rows.  q / dO / O / dq bf16 [B*R, n_q*128] sample-major (row b*R + r), dk / dv bf16 [B*R, n_kv*128]; K / VT = one
+ * layer of the cache, sample b at element offset b*k_bs / b*vt_bs; valid_len = DEVICE int32[B] (clamped to [0, blk_start] in the kernel); ws = B *
+ * vlaser_attn_rows_bwd_ws_floats(n_q) floats.  Needs 1 <= R <= 16, B >= 1, blk_start + R <= min(s_max, 2048), K 16-byte aligned, k_bs % 8 == 0.  Same arithmetic in the same
+ * order per (sample, head, row), same fixed-order dK / dV sum: bit-identical to B calls of vlaser_attn_rows_bwd on the samples' cache slices. */
+int vlaser_attn_rows_bwd_batched(const void* q, const void* K, const void* VT, const void* dO, const void* O, void* dq, void* dk, void* dv, int B, int R, int n_q,
+                                 int n_kv, int s_max, long long k_bs, long long vt_bs, const int32_t* valid_len, int blk_start, int first_tok_self, float scale,
+                                 float* ws, vl_stream_t stream);
 
 /* ---- f1 with `train_vlm: True` (ABI 4, r03): the reference's second parameter group `trainable_vlm_parameters` (pizero_internvl.py:405-411 =
  * vision tower + projector + the VLM mixture's decoder layers; optimiser + schedule train.py:270-295, stepped :509-520).  The gradient reaches the

@@ -90,6 +90,7 @@ _SIGS = {
     'vlaser_argmax': [vp, i32, i32, vp, vp, vp, i32, vp, i32, vp],
     'vlaser_argmax_ws_bytes': [i32],
     'vlaser_vla_prep': [vp, vp, vp, vp, i32, i32, i32, f32, f32, vp],
+    'vlaser_vla_prep_rows': [vp, vp, vp, vp, i32, i32, i32, vp, i32, f32, vp],
     'vlaser_small_linear': [vp, vp, vp, vp, i32, i32, i32, vp],
     'vlaser_vla_step': [vp, vp, i32, i32, i32, vp, f32, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     'vlaser_vla_euler': [vp, vp, i32, i32, vp, f32, vp, vp, vp, i32, i32, f32, f32, i32, vp, vp, vp, i32, i32, i32, vp],
@@ -129,6 +130,7 @@ _SIGS = {
     'vlaser_silu_bwd': [vp, vp, vp, i64, vp],
     'vlaser_attn_rows_bwd': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp],
     'vlaser_attn_rows_bwd_ex': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp],
+    'vlaser_attn_rows_bwd_batched': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, vp, i32, i32, f32, vp, vp],
     'vlaser_attn_rows_bwd_ws_floats': [i32],
     'vlaser_attn_bwd_pds_masked': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, vp],
     'vlaser_rope_bwd_pack_ex': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp],

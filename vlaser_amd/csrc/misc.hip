@@ -456,6 +456,33 @@ extern "C" int vlaser_vla_prep(const float* action, const void* w1, const void* 
   return 0;
 }
 
+// vla_prep with one flow-matching time per sample (PiZero.forward at batch B, pizero_internvl.py:1064-1197): row m uses t[m / rows_per_t]; per row the arithmetic is
+// vla_prep_kernel's, so a row is bit-identical to vlaser_vla_prep called with that scalar.
+__global__ __launch_bounds__(256) void vla_prep_rows_kernel(const float* __restrict__ action, const bf16_t* __restrict__ w1,
+                                                            const bf16_t* __restrict__ b1, bf16_t* __restrict__ xcat, int Wd, int adim,
+                                                            const float* __restrict__ t_tab, int rows_per_t, float max_period) {
+  const int m = blockIdx.x;
+  const float t = t_tab[m / rows_per_t];
+  const int half = Wd / 2;
+  const float e = logf(max_period) / (float)(half - 1);
+  for (int c = threadIdx.x; c < Wd; c += 256) {
+    const int i = c < half ? c : c - half;
+    const float ang = t * expf(-e * (float)i);
+    xcat[(size_t)m * 2 * Wd + c] = f32_to_bf16(c < half ? sinf(ang) : cosf(ang));
+    float acc = bf16_to_f32(b1[c]);
+    for (int k = 0; k < adim; ++k) acc += bf16_to_f32(f32_to_bf16(action[m * adim + k])) * bf16_to_f32(w1[c * adim + k]);
+    xcat[(size_t)m * 2 * Wd + Wd + c] = f32_to_bf16(acc);
+  }
+}
+extern "C" int vlaser_vla_prep_rows(const float* action, const void* w1, const void* b1, void* xcat, int M, int Wd, int adim, const float* t, int rows_per_t,
+                                    float max_period, vl_stream_t s) {
+  VL_CHECK(action && w1 && b1 && xcat && t && M > 0 && Wd >= 4 && adim > 0 && rows_per_t > 0, "vlaser_vla_prep_rows: bad args (t = device float[ceil(M / rows_per_t)])");
+  hipLaunchKernelGGL(vla_prep_rows_kernel, dim3(M), dim3(256), 0, (hipStream_t)s, action, (const bf16_t*)w1, (const bf16_t*)b1, (bf16_t*)xcat,
+                     Wd, adim, t, rows_per_t, max_period);
+  VL_LAUNCH_CHECK();
+  return 0;
+}
+
 // proprio encoder: out[m, :] = Wp p[m] + bp  (pizero_internvl.py:823).
 __global__ __launch_bounds__(256) void small_linear_kernel(const float* __restrict__ x, const bf16_t* __restrict__ w, const bf16_t* __restrict__ b,
                                                            bf16_t* __restrict__ out, int N, int K) {

@@ -1226,6 +1226,132 @@ extern "C" int vlaser_attn_rows_bwd_ex(const void* q, const void* K, const void*
   return 0;
 }
 
+// B samples' expert rows in ONE call (VLATrainer(batch_rows=True)): sample b of blockIdx.z owns rows [b R, (b + 1) R) of the sample-major q / dO / O / dq, slice b of the
+// cache (element strides k_bs / vt_bs), entry b of the device valid_len table (clamped to blk_start) and slab b of the workspace.  The arithmetic of one (sample, head, row)
+// is attn_rows_bwd_kernel's, statement by statement and in the same order, so the result is bit-identical to B calls of vlaser_attn_rows_bwd on the samples' cache slices;
+// the weights of the 28 layers are not involved here, what the batch buys is 2 launches per layer instead of 2 B.
+__global__ __launch_bounds__(256) void attn_rows_bwd_batched_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ VT,
+                                                                    const bf16_t* __restrict__ dO, const bf16_t* __restrict__ O, bf16_t* __restrict__ dq,
+                                                                    float* __restrict__ ws, int R, int n_q, int n_kv, int s_max, long long k_bs, long long vt_bs,
+                                                                    const int32_t* __restrict__ valid_len_tab, int blk_start, int first_tok_self, float scale) {
+  __shared__ float sc[ARB_MAXKEYS];       // p, then dS
+  __shared__ float qs[128], dos[128], red[8];
+  const int h = blockIdx.x, r = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int G = n_q / n_kv, kvh = h / G, kv_len = blk_start + R;
+  const int vl = valid_len_tab[b], valid_len = vl < 0 ? 0 : (vl > blk_start ? blk_start : vl);
+  const bf16_t* Kh = K + (size_t)b * k_bs + (size_t)kvh * s_max * 128;
+  const bf16_t* Vh = VT + (size_t)b * vt_bs + (size_t)kvh * 128 * s_max;
+  ws += (size_t)b * n_q * 512;
+  float* p_blk = ws + ((size_t)h * 16 + r) * 16;                       // [n_q][16][16] P of the block keys, then the same for dS
+  float* ds_blk = ws + (size_t)n_q * 256 + ((size_t)h * 16 + r) * 16;
+  auto block_sum = [&](float v) {
+    v = wave_sum(v);
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    const float t = red[0] + red[1] + red[2] + red[3];
+    __syncthreads();
+    return t;
+  };
+  auto block_max = [&](float v) {
+    v = wave_max(v);
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    const float t = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    return t;
+  };
+  const size_t ro = ((size_t)b * R + r) * n_q * 128 + (size_t)h * 128;
+  if (tid < 128) { qs[tid] = bf16_to_f32(q[ro + tid]); dos[tid] = bf16_to_f32(dO[ro + tid]); }
+  __syncthreads();
+  const int hi2 = (r == 0 && first_tok_self) ? blk_start + 1 : kv_len;
+  float mx = -3.0e38f;
+  for (int j = tid; j < kv_len; j += 256) {
+    const bool vis = j < valid_len || (j >= blk_start && j < hi2);
+    float s = -3.0e38f;
+    if (vis) {
+      float a = 0.f;
+      const bf16_t* kr = Kh + (size_t)j * 128;
+#pragma unroll
+      for (int d8 = 0; d8 < 16; ++d8) {
+        const u32x4 kv = *reinterpret_cast<const u32x4*>(kr + d8 * 8);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { a += qs[d8 * 8 + 2 * e] * bf16lo_to_f32(kv[e]); a += qs[d8 * 8 + 2 * e + 1] * bf16hi_to_f32(kv[e]); }
+      }
+      s = a * scale;
+    }
+    sc[j] = s;
+    mx = fmaxf(mx, s);
+  }
+  mx = block_max(mx);
+  float sum = 0.f;
+  for (int j = tid; j < kv_len; j += 256) {
+    const float p = sc[j] > -1.0e38f ? __expf(sc[j] - mx) : 0.f;
+    sc[j] = p;
+    sum += p;
+  }
+  sum = block_sum(sum);
+  const float inv = 1.0f / sum;
+  float dd = 0.f;
+  if (tid < 128) dd = dos[tid] * bf16_to_f32(O[ro + tid]);
+  const float D = block_sum(dd);
+  for (int j = tid; j < kv_len; j += 256) {
+    const float p = sc[j] * inv;
+    float ds = 0.f;
+    if (p > 0.f) {
+      float dp = 0.f;
+#pragma unroll 8
+      for (int d = 0; d < 128; ++d) dp += dos[d] * bf16_to_f32(Vh[(size_t)d * s_max + j]);
+      ds = p * (dp - D) * scale;
+    }
+    if (j >= blk_start) { p_blk[j - blk_start] = p; ds_blk[j - blk_start] = ds; }
+    sc[j] = ds;
+  }
+  __syncthreads();
+  {
+    const int d = tid & 127, half = tid >> 7;
+    float a = 0.f;
+    for (int j = half; j < kv_len; j += 2) a += sc[j] * bf16_to_f32(Kh[(size_t)j * 128 + d]);
+    if (half == 1) qs[d] = a;                       // qs is free now
+    __syncthreads();
+    if (half == 0) dq[ro + d] = f32_to_bf16(a + qs[d]);
+  }
+}
+// attn_rows_bwd_kv_kernel per sample (blockIdx.z): head group outer, row inner, no atomics
+__global__ __launch_bounds__(128) void attn_rows_bwd_kv_batched_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ dO, const float* __restrict__ ws,
+                                                                       bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int R, int n_q, int n_kv) {
+  const int kvh = blockIdx.x, jb = blockIdx.y, b = blockIdx.z, d = threadIdx.x, G = n_q / n_kv;
+  ws += (size_t)b * n_q * 512;
+  float ak = 0.f, av = 0.f;
+  for (int hg = 0; hg < G; ++hg) {
+    const int h = kvh * G + hg;
+    for (int r = 0; r < R; ++r) {
+      const size_t ro = ((size_t)b * R + r) * n_q * 128 + (size_t)h * 128 + d;
+      const float p = ws[((size_t)h * 16 + r) * 16 + jb], ds = ws[(size_t)n_q * 256 + ((size_t)h * 16 + r) * 16 + jb];
+      av += p * bf16_to_f32(dO[ro]);
+      ak += ds * bf16_to_f32(q[ro]);
+    }
+  }
+  dk[((size_t)b * R + jb) * n_kv * 128 + kvh * 128 + d] = f32_to_bf16(ak);
+  dv[((size_t)b * R + jb) * n_kv * 128 + kvh * 128 + d] = f32_to_bf16(av);
+}
+extern "C" int vlaser_attn_rows_bwd_batched(const void* q, const void* K, const void* VT, const void* dO, const void* O, void* dq, void* dk, void* dv, int B, int R,
+                                            int n_q, int n_kv, int s_max, long long k_bs, long long vt_bs, const int32_t* valid_len, int blk_start,
+                                            int first_tok_self, float scale, float* ws, vl_stream_t s) {
+  VL_CHECK(q && K && VT && dO && O && dq && dk && dv && ws && valid_len,
+           "vlaser_attn_rows_bwd_batched: null pointer (ws = B * vlaser_attn_rows_bwd_ws_floats(n_q) floats, valid_len = device int32[B])");
+  VL_CHECK(B >= 1 && B <= 65535 && R >= 1 && R <= 16 && n_q > 0 && n_kv > 0 && n_q % n_kv == 0 && blk_start >= 0 && blk_start + R <= s_max &&
+           blk_start + R <= ARB_MAXKEYS, "vlaser_attn_rows_bwd_batched: bad geometry (B >= 1, 1 <= R <= 16, kv_len <= min(s_max, %d))", ARB_MAXKEYS);
+  VL_CHECK((((uintptr_t)K) & 15) == 0 && s_max % 8 == 0 && k_bs % 8 == 0 && k_bs >= (long long)n_kv * s_max * 128 && vt_bs >= (long long)n_kv * s_max * 128,
+           "vlaser_attn_rows_bwd_batched: the K cache must be 16-byte aligned, k_bs a multiple of 8, and a batch stride no shorter than one sample's [n_kv, s_max, 128]");
+  hipLaunchKernelGGL(attn_rows_bwd_batched_kernel, dim3(n_q, R, B), dim3(256), 0, (hipStream_t)s, (const bf16_t*)q, (const bf16_t*)K, (const bf16_t*)VT,
+                     (const bf16_t*)dO, (const bf16_t*)O, (bf16_t*)dq, ws, R, n_q, n_kv, s_max, k_bs, vt_bs, valid_len, blk_start, first_tok_self, scale);
+  VL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(attn_rows_bwd_kv_batched_kernel, dim3(n_kv, R, B), dim3(128), 0, (hipStream_t)s, (const bf16_t*)q, (const bf16_t*)dO, ws, (bf16_t*)dk,
+                     (bf16_t*)dv, R, n_q, n_kv);
+  VL_LAUNCH_CHECK();
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------------- LayerNorm backward (ViT blocks, f1: train_vlm)
 // y = gamma * xhat + beta, xhat = (x - mean) rs.  g = gamma dy;  dx = rs * (g - mean(g) - xhat * mean(g xhat));  dx_out = dres + dx.
 // One wave per row (C <= 8192).  The affine gradients are column sums over the rows: vlaser_colsum_mul mode 3 (gamma) and mode 0 (beta).

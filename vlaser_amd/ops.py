@@ -624,6 +624,13 @@ def vla_prep(action, w1, b1, xcat, M, W, adim, t, max_period):
                                     _stream()), 'vlaser_vla_prep')
 
 
+def vla_prep_rows(action, w1, b1, xcat, M, W, adim, t, rows_per_t, max_period):
+    """vla_prep with a device fp32 `t` [ceil(M / rows_per_t)]: row m uses t[m // rows_per_t] (one flow-matching time per sample)."""
+    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and rows_per_t > 0 and t.numel() * rows_per_t >= M
+    L.check(L.lib().vlaser_vla_prep_rows(action.data_ptr(), w1.data_ptr(), b1.data_ptr(), xcat.data_ptr(), M, W, adim, t.data_ptr(), rows_per_t, max_period,
+                                         _stream()), 'vlaser_vla_prep_rows')
+
+
 def small_linear(x, w, b, out, M, N, K):
     L.check(L.lib().vlaser_small_linear(x.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), M, N, K, _stream()),
             'vlaser_small_linear')
@@ -1062,6 +1069,24 @@ def attn_rows_bwd(q, K, VT, dO, O, dq, dk, dv, R, n_q, n_kv, s_max, valid_len, b
     L.check(L.lib().vlaser_attn_rows_bwd_ex(q.data_ptr(), K.data_ptr(), VT.data_ptr(), dO.data_ptr(), O.data_ptr(), dq.data_ptr(), dk.data_ptr(),
                                             dv.data_ptr(), R, n_q, n_kv, s_max, valid_len, blk_start, int(first_tok_self), scale, _p(p_out), _p(ds_out),
                                             ws.data_ptr(), _stream()), 'vlaser_attn_rows_bwd')
+
+
+
+def attn_rows_bwd_batched(q, K, VT, dO, O, dq, dk, dv, B, R, n_q, n_kv, s_max, valid_len, blk_start, first_tok_self, scale, ws=None):
+    """attn_rows_bwd for the expert rows of B samples in one call: q / dO / O / dq [B*R, n_q*128] sample-major, dk / dv [B*R, n_kv*128], K / VT = one layer of the
+    cache [>= B, n_kv, s_max, 128] / [>= B, n_kv, 128, s_max] (batch strides taken from the tensors), valid_len = device int32 [B]."""
+    nws = B * L.lib().vlaser_attn_rows_bwd_ws_floats(n_q)
+    if ws is None:
+        ws = torch.empty(nws, dtype=torch.float32, device=q.device)
+    assert ws.dtype == torch.float32 and ws.numel() >= nws
+    assert valid_len.is_cuda and valid_len.dtype == torch.int32 and valid_len.is_contiguous() and valid_len.numel() >= B
+    assert K.dim() == 4 and VT.dim() == 4 and K.shape[0] >= B and VT.shape[0] >= B and K[0].is_contiguous() and VT[0].is_contiguous()
+    assert tuple(K.shape[1:]) == (n_kv, s_max, 128) and tuple(VT.shape[1:]) == (n_kv, 128, s_max)
+    for t, w in ((q, n_q), (dO, n_q), (O, n_q), (dq, n_q), (dk, n_kv), (dv, n_kv)):
+        assert t.is_contiguous() and t.numel() >= B * R * w * 128
+    L.check(L.lib().vlaser_attn_rows_bwd_batched(q.data_ptr(), K.data_ptr(), VT.data_ptr(), dO.data_ptr(), O.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                                                 B, R, n_q, n_kv, s_max, K.stride(0), VT.stride(0), valid_len.data_ptr(), blk_start, int(first_tok_self), scale,
+                                                 ws.data_ptr(), _stream()), 'vlaser_attn_rows_bwd_batched')
 
 
 # ------------------------------------------------------------------------------------------------ f1 with train_vlm: VLM-side backward

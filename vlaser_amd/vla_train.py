@@ -18,6 +18,10 @@ Mirrors the step semantics of the reference's VLA trainer without its control pl
 The 5 expert rows (proprio + 4 action tokens) go through the MFMA GEMM kernels with every intermediate saved; their backward reuses
 the SFT kernels (dgrad on resident W^T, TN wgrad, RMSNorm / SwiGLU / RoPE backward) plus `vlaser_attn_rows_bwd` for the joint
 attention.  All arithmetic is HIP; torch holds buffers, streams and RCCL.
+
+`VLATrainer(batch_rows=True, max_batch=32)` (opt-in) runs a per-device batch as the reference collates it -- ONE `[B, ...]` pass over B*R sample-major
+expert rows and B*T prefix rows (`forward_backward_batch`, `vlaser_attn_rows_bwd_batched`, `vlaser_vla_prep_rows`) instead of B one-sample passes:
+the expert's weights are streamed once per group, not once per sample (profiles/vla_batch_rows_ab.md).  Action-expert group only.
 """
 import math
 import os
@@ -26,7 +30,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib as L
-from . import ops, prep
+from . import backward, ops, prep
 from .config import VLAConfig
 from .engine import BF, KVCache, PrefillBuffers, QwenStack, VitEngine, prefill_begin, prefill_layer
 from .pizero import canonicalize_vla_state_dict, stage_pixels
@@ -59,6 +63,19 @@ def cosine_warmup_restarts_lr(step, first_cycle_steps, max_lr, min_lr=0.0, warmu
     if in_cycle < warmup_steps:
         return (mx - min_lr) * in_cycle / warmup_steps + min_lr
     return min_lr + (mx - min_lr) * (1 + math.cos(math.pi * (in_cycle - warmup_steps) / (cur - warmup_steps))) / 2
+
+
+def plan_row_groups(n_samples, max_batch):
+    """`VLATrainer(batch_rows=True).step`: [(lo, hi, weight)] -- consecutive groups of at most `max_batch` samples, each ONE forward/backward pass; group
+    [lo, hi) weighs (hi - lo) / n_samples in the step's mean loss and gradient."""
+    if n_samples < 1 or max_batch < 1:
+        raise ValueError(f'plan_row_groups: need n_samples >= 1 and max_batch >= 1 (got {n_samples}, {max_batch})')
+    return [(lo, min(lo + max_batch, n_samples), (min(lo + max_batch, n_samples) - lo) / n_samples) for lo in range(0, n_samples, max_batch)]
+
+
+def expert_row(b, r, R):
+    """Row of sample b's expert token r (0 = proprio, 1..na = action tokens) in the sample-major [B*R, ...] buffers of the batched pass."""
+    return b * R + r
 
 
 class ModelAveraging:
@@ -121,11 +138,21 @@ class ModelAveraging:
 
 
 class VLATrainer(ParamGroup):
-    """`step(batch...)` = one optimizer update of the action expert on flow-matching samples (per-device batch B >= 1, sample by sample)."""
+    """`step(batch...)` = one optimizer update of the action expert on flow-matching samples (per-device batch B >= 1): sample by sample, or with
+    `batch_rows=True` in groups of up to `max_batch` samples that run as ONE forward/backward pass over their B*R expert rows and B*T prefix rows
+    (`forward_backward_batch`; the reference collates 32 samples per device into one `PiZero.forward` call, slurm/train_internvl.sh).  The batched
+    pass covers the action-expert group only: `train_vlm=True` refuses it."""
 
     def __init__(self, cfg: VLAConfig, device='cuda', lr=5e-5, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
-                 process_group=None, bucket_layers=8, train_vlm=False, vlm_lr=5e-5, vlm_weight_decay=0.0, optimizer='adamw'):
+                 process_group=None, bucket_layers=8, train_vlm=False, vlm_lr=5e-5, vlm_weight_decay=0.0, optimizer='adamw', batch_rows=False,
+                 max_batch=32):
         L.lib()
+        if batch_rows and train_vlm:
+            raise ValueError("batch_rows=True does not cover train_vlm=True: the VLM group's backward (vla_vlm_group.py, vlaser_attn_rows_bwd_ex and the "
+                             'per-sample prefix dK / dV behind it) is not batched')
+        if batch_rows and not (isinstance(max_batch, int) and max_batch >= 1):
+            raise ValueError(f'max_batch must be a positive int (got {max_batch!r})')
+        self.batch_rows, self.max_batch = bool(batch_rows), max_batch if batch_rows else 1
         # 'adamw8bit': both groups keep block-wise 8-bit moments, as the reference builds both of its optimizers (bnb.optim.AdamW8bit, train.py:251-255,278-282)
         self.optimizer = check_optimizer(optimizer)
         if not torch.cuda.is_available():
@@ -150,7 +177,7 @@ class VLATrainer(ParamGroup):
         sd = canonicalize_vla_state_dict(sd)
         cfg, dev, ex = self.cfg, self.device, self.cfg.expert
         base, llm = cfg.base, cfg.base.llm
-        self.vit = VitEngine(sd, base, dev, max_tiles=1)
+        self.vit = VitEngine(sd, base, dev, max_tiles=self.max_batch)
         self.vlm = QwenStack(sd, 'language_model.', llm, dev, with_embed=True, with_head=False, gemm=True, skinny=False)      # frozen
         H, A, P = ex.hidden_size, cfg.action_dim, cfg.proprio_dim
         self.A8 = 8                                 # tiny operands are padded to the kernels' 8-column granularity
@@ -191,40 +218,55 @@ class VLATrainer(ParamGroup):
         nq, nkv, hd = ex.num_attention_heads, ex.num_key_value_heads, ex.head_dim
         NQ, Lyr, R, T = (nq + 2 * nkv) * hd, ex.num_hidden_layers, self.R, self.T
         z = lambda *s, dt=BF: torch.zeros(*s, dtype=dt, device=dev)
+        # batch_rows: every 16-row buffer below holds the max_batch * R sample-major expert rows, the prefix buffers max_batch * T rows; off: 16 rows / T rows as ever
+        MB = self.max_batch
+        RW = self.rows = max(16, MB * R) if self.batch_rows else 16
         self.s_max = (T + R + 63) // 64 * 64
-        self.cache = KVCache(llm.num_hidden_layers, 1, llm.num_key_value_heads, self.s_max, dev, llm.head_dim)
-        self.pbuf = PrefillBuffers(self.vlm, T, dev)
+        self.cache = KVCache(llm.num_hidden_layers, MB, llm.num_key_value_heads, self.s_max, dev, llm.head_dim)
+        self.pbuf = PrefillBuffers(self.vlm, MB * T, dev)
         self.rope = ops.rope_table(T + 16, llm.head_dim, llm.rope_theta, dev)
-        self.h_vlm = z(T, llm.hidden_size)
-        self.rank_ws = z(T, dt=torch.int32)
-        self.valid_len = z(1, dt=torch.int32)
-        self.pos_vlm, self.pos5 = z(T, dt=torch.int32), z(16, dt=torch.int32)
+        self.h_vlm = z(MB * T, llm.hidden_size)
+        self.rank_ws = z(MB * T, dt=torch.int32)
+        self.valid_len = z(MB, dt=torch.int32)
+        self.pos_vlm, self.pos5 = z(T, dt=torch.int32), z(RW, dt=torch.int32)
         # the dgrad GEMMs read the weights as stored (vlaser_gemm_nn); only the 7-row action decoder keeps a zero-padded transposed copy
         # saved activations of the R expert rows (tiny: R x width per layer)
-        self.h_in = z(Lyr + 1, 16, H)
-        self.x1, self.x2, self.h2 = z(Lyr, 16, H), z(Lyr, 16, H), z(Lyr, 16, H)
-        self.q, self.ao = z(Lyr, 16, nq * hd), z(Lyr, 16, nq * hd)
-        self.gu, self.act = z(Lyr, 16, 2 * I), z(Lyr, 16, I)
-        self.part = torch.zeros(16 * 16 * max(H, 2 * I), dtype=F32, device=dev)
-        self.xcat, self.z2, self.e2 = z(16, 2 * H), z(16, H), z(16, H)
-        self.hn, self.vout = z(16, H), torch.zeros(16, self.A8, dtype=F32, device=dev)
-        self.psi = torch.zeros(16, cfg.action_dim, dtype=F32, device=dev)
-        self.proprio = torch.zeros(1, cfg.proprio_dim, dtype=F32, device=dev)
+        self.h_in = z(Lyr + 1, RW, H)
+        self.x1, self.x2, self.h2 = z(Lyr, RW, H), z(Lyr, RW, H), z(Lyr, RW, H)
+        self.q, self.ao = z(Lyr, RW, nq * hd), z(Lyr, RW, nq * hd)
+        self.gu, self.act = z(Lyr, RW, 2 * I), z(Lyr, RW, I)
+        self.part = torch.zeros(8 * RW * H if self.batch_rows else 16 * 16 * max(H, 2 * I), dtype=F32, device=dev)      # <= 8 split-K slabs of [rows, H] (o_proj / down_proj)
+        self.xcat, self.z2, self.e2 = z(RW, 2 * H), z(RW, H), z(RW, H)
+        self.hn, self.vout = z(RW, H), torch.zeros(RW, self.A8, dtype=F32, device=dev)
+        self.psi = torch.zeros(RW, cfg.action_dim, dtype=F32, device=dev)
+        self.proprio = torch.zeros(MB, cfg.proprio_dim, dtype=F32, device=dev)
         # backward buffers
-        self.dh, self.dh2, self.dx = z(16, H), z(16, H), z(16, H)
-        self.dact, self.dgu = z(16, I), z(16, 2 * I)
-        self.dao, self.dq = z(16, nq * hd), z(16, nq * hd)
-        self.dgrad_part = torch.zeros(40 * 16 * 1536, dtype=F32, device=self.device)      # split-K slabs of the long-contraction dgrads (_dgrad)
-        self.arb_ws = torch.zeros(L.lib().vlaser_attn_rows_bwd_ws_floats(nq), dtype=F32, device=self.device)      # block-key P / dS of vlaser_attn_rows_bwd
-        self.dk, self.dv = z(16, nkv * hd), z(16, nkv * hd)
-        self.dqkv = z(16, NQ)
-        self.dv64, self.decT = z(16, 64), z(H, 64)
+        self.dh, self.dh2, self.dx = z(RW, H), z(RW, H), z(RW, H)
+        self.dact, self.dgu = z(RW, I), z(RW, 2 * I)
+        self.dao, self.dq = z(RW, nq * hd), z(RW, nq * hd)
+        # split-K slabs of the long-contraction dgrads (_dgrad); batch_rows: also up to 8 slabs of [rows, widest dgrad output] for the > 16-row rule
+        self.dgrad_part = torch.zeros(max(40 * 16 * 1536, 8 * RW * max(H, nq * hd) if self.batch_rows else 0), dtype=F32, device=self.device)
+        self.arb_ws = torch.zeros(MB * L.lib().vlaser_attn_rows_bwd_ws_floats(nq), dtype=F32, device=self.device)      # block-key P / dS of vlaser_attn_rows_bwd, per sample
+        self.dk, self.dv = z(RW, nkv * hd), z(RW, nkv * hd)
+        self.dqkv = z(RW, NQ)
+        self.dv64, self.decT = z(RW, 64), z(H, 64)
         self.col = torch.zeros(max(2 * I, NQ, 2 * H), dtype=F32, device=dev)
-        self.rowstat = torch.zeros(2 * 16 + 16 * max(2 * I, NQ, 2 * H), dtype=F32, device=dev)
-        self.normw_ws = torch.zeros(8 * H, dtype=F32, device=dev)
+        self.rowstat = torch.zeros(2 * RW + RW * max(2 * I, NQ, 2 * H), dtype=F32, device=dev)
+        self.normw_ws = torch.zeros(RW // 2 * H, dtype=F32, device=dev)
         self.gnorm2 = torch.zeros(1, dtype=F32, device=dev)
         self.sumsq_ws = torch.zeros(1024, dtype=F32, device=dev)
         self.comm_stream = torch.cuda.Stream(device=dev) if self.dp_active else None
+        if self.batch_rows:
+            P8 = (max(cfg.proprio_dim, cfg.action_dim) + 7) // 8 * 8
+            rows8 = (MB * self.na + 7) // 8 * 8
+            self.pos_vlm_b, self.t_dev = z(MB * T, dt=torch.int32), torch.zeros(MB, dtype=F32, device=dev)
+            self.pro_h = z(MB, H)                                   # proprio encoder output, one row per sample (scattered to rows b*R)
+            self.act_rows, self.dact_rows = z(RW, H), z(RW, H)      # the action rows of h / dh, gathered from / scattered to the sample-major buffers
+            # the tiny padded operands of the encoder / decoder weight gradients: contraction rows grow to B (proprio) and B*na (action), 8-row granularity
+            self.wg8, self.pw8, self.aw8 = z(8, H), z(H, P8), z(H, P8)
+            self.p8, self.d8 = z((MB + 7) // 8 * 8, P8), z((MB + 7) // 8 * 8, H)
+            self.a8, self.l8 = z(rows8, P8), z(rows8, H)
+            self.dxc = z(RW, 2 * H)
 
     def _refresh_transposes(self):
         v = self.fp.view
@@ -238,6 +280,9 @@ class VLATrainer(ParamGroup):
         ([5, 17920] @ [17920, 768]) has six output tiles, i.e. six workgroups pulling 27.5 MB (~80 us, r06ab trace); as many split-K slices as divide the
         contraction put 240 workgroups on it, the fp32 slabs (a few hundred KB) are summed in slab order by one launch -- the rule of the SFT step's head dgrad."""
         Nin, Kout = W.shape
+        if M > 16:          # batch_rows: row tiles, not a weight stream -- the rule the SFT step measured for its dgrads (backward.dgrad_nn; profiles/vla_batch_rows_ab.md)
+            backward.dgrad_nn(dY[:M], W, out[:M], self.dgrad_part)
+            return
         if Nin > 2048 and Kout <= 4096 and Kout % 8 == 0:
             sp = max(d for d in range(1, 41) if Nin % (64 * d) == 0)
             if sp > 8 and sp * M * Kout <= self.dgrad_part.numel():
@@ -403,6 +448,168 @@ class VLATrainer(ParamGroup):
             self.vg.backward_tail(ids_h)                # mlp1, pixel_shuffle, the vision tower and its embeddings
         return loss
 
+    # ------------------------------------------------------------------ forward + backward of B samples as ONE pass (batch_rows=True)
+    def forward_backward_batch(self, input_ids, pixel_values, proprios, actions, t, x0, vlm_position_ids=None, proprio_position_ids=None,
+                               action_position_ids=None, causal_mask=None, on_bucket_ready=None):
+        """`PiZero.forward` (pizero_internvl.py:1064-1197) + backward on a collated batch: input_ids [B,T] (every sample right-padded), pixel_values
+        [B,3,448,448], proprios [B,1,P], actions / x0 [B,na,A], t [B].  Returns the batch-mean loss (mean over B*na*A elements, device scalar) and leaves the
+        gradients of that mean in self.fp.g.  The expert rows are sample-major (`expert_row`: row b*R + r, r = 0 the proprio token), the frozen prefix
+        runs at batch B as the inference prefill does; each launch is the one-sample step's with B times the rows, so at B = 1 the bits are its bits."""
+        if not self.batch_rows:
+            raise ValueError('forward_backward_batch needs VLATrainer(batch_rows=True): the buffers of the default trainer hold one sample')
+        cfg, dev, ex, llm = self.cfg, self.device, self.cfg.expert, self.cfg.base.llm
+        T, na, R = self.T, self.na, self.R
+        H, I, A, P = ex.hidden_size, ex.intermediate_size, cfg.action_dim, cfg.proprio_dim
+        nq, nkv, hd = ex.num_attention_heads, ex.num_key_value_heads, ex.head_dim
+        Lyr = ex.num_hidden_layers
+        v, gv = self.fp.view, self.fp.gview
+        ids_h = input_ids.detach().to('cpu', torch.int64).reshape(-1, T)
+        B = ids_h.shape[0]
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f'forward_backward_batch: {B} samples do not fit max_batch={self.max_batch}')
+        M, Ma = B * R, B * na                       # expert rows, action rows
+        pad = ids_h == cfg.base.pad_token_id
+        counts = (~pad).sum(1).tolist()
+        for b, n_valid in enumerate(counts):
+            if n_valid < T and bool(pad[b, :n_valid].any()):
+                raise ValueError(f'input_ids must be right-padded: sample {b} has pad tokens inside its valid prefix, which is not supported')
+        if causal_mask is not None:
+            prep.check_block_mask(causal_mask, counts, T, 1, na)
+        sig = cfg.flow_sig_min
+        tv = t.detach().to('cpu', torch.float64).reshape(-1).tolist()
+        assert len(tv) == B, (len(tv), B)
+        # ---- frozen prefix at batch B: ViT -> projector -> embeddings -> VLM layers (inference kernels), K / V^T of every layer cached per sample
+        pvb = stage_pixels(pixel_values, torch.empty(pixel_values.shape, dtype=BF, device=dev), dev)
+        ids = ids_h.reshape(-1).pin_memory().to(dev, non_blocking=True)
+        self.valid_len[:B].copy_(torch.tensor(counts, dtype=torch.int32).pin_memory(), non_blocking=True)      # from the host count: no device sync
+        bpos = lambda p, default, n: (default.expand(B, n) if p is None else p).to(torch.int32).reshape(B * n)
+        pos_vlm = self.pos_vlm_b[:B * T]
+        pos_vlm.copy_(bpos(vlm_position_ids, torch.arange(1, T + 1)[None], T))
+        pos5 = self.pos5[:M].view(B, R)
+        pos5[:, 0].copy_(bpos(proprio_position_ids, torch.ones(1, 1, dtype=torch.long), 1))
+        pos5[:, 1:].copy_(bpos(action_position_ids, torch.arange(2, 2 + na)[None], na).view(B, na))
+        h_vlm = self.h_vlm[:B * T]
+        feats = self.vit.forward(pvb)
+        ops.embed_merge(ids, self.vlm.embed, feats, h_vlm, cfg.base.img_context_token_id, cfg.base.pad_token_id, True, self.rank_ws)
+        nLv = llm.num_hidden_layers
+        prefill_begin(self.vlm, self.pbuf, h_vlm, B * T)
+        for i in range(nLv):
+            last = i == nLv - 1
+            prefill_layer(self.vlm, self.vlm.layers[i], self.pbuf, h_vlm, self.cache, i, self.rope, pos_vlm, B, T, L.ATTN_PREFIX,
+                          valid_len=self.valid_len, blk_start=T, skip_post_attn=last, next_norm_w=None if last else self.vlm.layers[i + 1].ln_in)
+        # ---- inputs of the expert rows: proprio encoder (rows b*R), action encoder on psi_t (rows b*R + 1 .. b*R + na)
+        x1a = actions.reshape(Ma, A).to(dev, F32)
+        x0a = x0.reshape(Ma, A).to(dev, F32)
+        # psi_t (:1050-1062) with the coefficients of each sample formed in double and rounded once, as the one-sample step's Python scalars are
+        c0 = torch.tensor([1 - (1 - sig) * x for x in tv], dtype=torch.float64).to(F32).to(dev).repeat_interleave(na)[:, None]
+        c1 = torch.tensor(tv, dtype=torch.float64).to(F32).to(dev)
+        self.t_dev[:B].copy_(c1)
+        self.psi[:Ma].copy_(c0 * x0a + c1.repeat_interleave(na)[:, None] * x1a)
+        self.proprio[:B].copy_(proprios.reshape(B, -1).to(dev, F32))
+        h0 = self.h_in[0, :M].view(B, R, H)
+        ops.small_linear(self.proprio, v['pe.w'], v['pe.b'], self.pro_h, B, H, P)
+        h0[:, 0].copy_(self.pro_h[:B])
+        ops.vla_prep_rows(self.psi, v['ae1.w'], v['ae1.b'], self.xcat, Ma, H, A, self.t_dev, na, cfg.time_max_period)       # [time embedding | linear_1(psi)]
+        self._linear(self.xcat, v['ae2.w'], v['ae2.b'], self.z2, Ma)
+        ops.silu(self.z2[:Ma], self.e2[:Ma])
+        self._linear(self.e2, v['ae3.w'], v['ae3.b'], self.act_rows, Ma)
+        h0[:, 1:].copy_(self.act_rows[:Ma].view(B, na, H))
+        # ---- expert layers on the B*R rows, everything saved
+        scale = hd ** -0.5
+        ks, vs = self.cache.strides()
+        for i in range(Lyr):
+            h_in, x1, x2, h2, q, ao, gu, act = self.h_in[i, :M], self.x1[i, :M], self.x2[i, :M], self.h2[i, :M], self.q[i, :M], self.ao[i, :M], self.gu[i, :M], self.act[i, :M]
+            ops.rmsnorm(h_in, v[f'l{i}.ln_in'], ex.rms_norm_eps, out=x1)
+            ops.gemm(L.EPI_QKV_ROPE, x1, v[f'l{i}.wqkv'], bias=v[f'l{i}.bqkv'], q_out=q, k_cache=self.cache.k[i], vt_cache=self.cache.vt[i], rope_cos=self.rope[0],
+                     rope_sin=self.rope[1], pos_ids=self.pos5, n_q_heads=nq, n_kv_heads=nkv, s_max=self.s_max, tok_per_batch=R, slot_base=T)
+            for (r0, nr, kvl) in ((0, 1, T + 1), (1, na, T + R)):            # proprio rows: prefix + themselves; action rows: prefix + whole block; batch stride = R rows
+                ops.attn_prefill(q[r0:], self.cache.k[i], self.cache.vt[i], ao[r0:], B, nr, kvl, nq, nkv, hd, (R * nq * hd, hd, nq * hd), ks, vs,
+                                 (R * nq * hd, nq * hd), self.s_max, scale, L.ATTN_PREFIX, valid_len=self.valid_len, blk_start=T, q_row_off=T + r0)
+            sp = ops.gemm_splits(M, H, nq * hd)
+            ops.gemm(L.EPI_PARTIAL, ao, v[f'l{i}.wo'], out_f32=self.part, k_splits=sp)
+            ops.reduce_norm(h_in, self.part, sp, M, H, h2, x2, norm=1, norm_w=v[f'l{i}.ln_post'], eps=ex.rms_norm_eps)
+            ops.gemm(L.EPI_NONE, x2, v[f'l{i}.wgu'], out=gu)
+            ops.swiglu(gu, act, M, I)
+            sp = ops.gemm_splits(M, H, I)
+            ops.gemm(L.EPI_PARTIAL, act, v[f'l{i}.wdown'], out_f32=self.part, k_splits=sp)
+            ops.reduce_norm(h2, self.part, sp, M, H, self.h_in[i + 1, :M])
+        # ---- head + loss on the action rows
+        h_fin = self.act_rows[:Ma]
+        h_fin.view(B, na, H).copy_(self.h_in[Lyr, :M].view(B, R, H)[:, 1:])
+        hn = self.hn[:Ma]
+        ops.rmsnorm(h_fin, v['norm'], ex.rms_norm_eps, out=hn)
+        vout = self.vout[:Ma]
+        ops.gemm(L.EPI_F32, hn, v['dec.w'], out=vout)                       # [B*na, A] (+ bias below), fp32
+        vel = vout[:, :A] + v['dec.b'].float()
+        diff = vel.to(BF).float() - (x1a - (1 - sig) * x0a)                 # the decoder is a bf16 Linear in the reference's bf16 training
+        loss = (diff * diff).mean()
+        dvel = diff * (2.0 / (Ma * A))                                      # d loss / d v of the batch mean
+        # ================================================================ backward
+        self.dv64.zero_()
+        self.dv64[:Ma, :A] = dvel.to(BF)
+        dv = self.dv64
+        ops.gemm_tn(dv[:Ma, :8], hn, self.wg8)                              # action decoder: dW = dv^T hn over the B*na rows (A padded to 8)
+        gv['dec.w'].copy_(self.wg8[:A])
+        gv['dec.b'].copy_(dvel.sum(0).to(BF))
+        dhn = self.dx[:Ma]
+        ops.gemm(L.EPI_NONE, dv[:Ma], self.decT, out=dhn)
+        dh = self.dh
+        dh.zero_()
+        dha = self.dact_rows[:Ma]
+        ops.rmsnorm_bwd(dhn, h_fin, v['norm'], None, dha, Ma, H, ex.rms_norm_eps, dw_out=gv['norm'], dw_ws=self.normw_ws)
+        dh[:M].view(B, R, H)[:, 1:].copy_(dha.view(B, na, H))              # the proprio rows get no gradient from the head
+        for i in reversed(range(Lyr)):
+            h_in, x1, x2, h2, q, ao, gu, act = self.h_in[i, :M], self.x1[i, :M], self.x2[i, :M], self.h2[i, :M], self.q[i, :M], self.ao[i, :M], self.gu[i, :M], self.act[i, :M]
+            dact, dgu, dx, dh2, dao = self.dact, self.dgu, self.dx, self.dh2, self.dao
+            self._dgrad(dh, v[f'l{i}.wdown'], dact, M)
+            self._wgrad(dh, act, gv[f'l{i}.wdown'], M)
+            ops.swiglu_bwd(gu, dact[:M], dgu[:M], M, I)
+            self._dgrad(dgu, v[f'l{i}.wgu'], dx, M)
+            self._wgrad(dgu, x2, gv[f'l{i}.wgu'], M)
+            ops.rmsnorm_bwd(dx[:M], h2, v[f'l{i}.ln_post'], dh[:M], dh2[:M], M, H, ex.rms_norm_eps, dw_out=gv[f'l{i}.ln_post'], dw_ws=self.normw_ws)
+            self._dgrad(dh2, v[f'l{i}.wo'], dao, M)
+            self._wgrad(dh2, ao, gv[f'l{i}.wo'], M)
+            ops.attn_rows_bwd_batched(q, self.cache.k[i], self.cache.vt[i], dao[:M], ao, self.dq[:M], self.dk[:M], self.dv[:M], B, R, nq, nkv, self.s_max,
+                                      self.valid_len, T, True, scale, ws=self.arb_ws)
+            ops.rope_bwd_pack(self.dq[:M], self.dk[:M], self.dv[:M], self.rope[0], self.rope[1], self.pos5, self.dqkv[:M], M, nq, nkv, kv_per_q_head=False)
+            self._dgrad(self.dqkv, v[f'l{i}.wqkv'], dx, M)
+            self._wgrad(self.dqkv, x1, gv[f'l{i}.wqkv'], M, bias_out=gv[f'l{i}.bqkv'])
+            ops.rmsnorm_bwd(dx[:M], h_in, v[f'l{i}.ln_in'], dh2[:M], dh[:M], M, H, ex.rms_norm_eps, dw_out=gv[f'l{i}.ln_in'], dw_ws=self.normw_ws)
+            if on_bucket_ready and (i == 0 or self.bucket_of_layer[i - 1] != self.bucket_of_layer[i]):
+                on_bucket_ready(self.bucket_of_layer[i])
+        # ---- encoders: proprio (rows b*R), action (rows b*R + 1 ..); the padded operands' contraction rows cover B and B*na
+        dhv = dh[:M].view(B, R, H)
+        B8, Ma8 = (B + 7) // 8 * 8, (Ma + 7) // 8 * 8
+        p8, d8 = self.p8[:B8], self.d8[:B8]
+        p8.zero_(); p8[:B, :P] = self.proprio[:B].to(BF)
+        d8.zero_(); d8[:B] = dhv[:, 0]
+        ops.gemm_tn(d8, p8, self.pw8)                                       # d pe.w = sum_b dh[b*R]^T proprio[b]
+        gv['pe.w'].copy_(self.pw8[:, :P])
+        if B == 1:
+            gv['pe.b'].copy_(d8[0])
+        else:
+            ops.colsum_bf16(d8, gv['pe.b'], B, H)
+        da = self.dact_rows
+        da[:Ma].view(B, na, H).copy_(dhv[:, 1:])
+        self._wgrad(da, self.e2, gv['ae3.w'], Ma, bias_out=gv['ae3.b'])
+        de2 = self.dx
+        self._dgrad(da, v['ae3.w'], de2, Ma)
+        dz2 = self.dh2
+        ops.silu_bwd(self.z2[:Ma], de2[:Ma], dz2[:Ma])
+        self._wgrad(dz2, self.xcat, gv['ae2.w'], Ma, bias_out=gv['ae2.b'])
+        dxc = self.dxc
+        self._dgrad(dz2, v['ae2.w'], dxc, Ma)
+        dl1 = dxc[:Ma, H:].contiguous()                                     # gradient of linear_1's output (the time half has no parameters)
+        a8, l8 = self.a8[:Ma8], self.l8[:Ma8]
+        a8.zero_(); a8[:Ma, :A] = self.psi[:Ma].to(BF)
+        l8.zero_(); l8[:Ma] = dl1
+        ops.gemm_tn(l8, a8, self.aw8)
+        gv['ae1.w'].copy_(self.aw8[:, :A])
+        ops.colsum_bf16(dl1, gv['ae1.b'], Ma, H)
+        if on_bucket_ready:
+            on_bucket_ready(len(self.buckets) - 1)
+        return loss
+
     # ------------------------------------------------------------------ optimizer / data parallel (the groups' per-bucket operations: param_group.py)
     def groups(self):
         """The trained parameter groups: the action expert (this object) and, with `train_vlm`, the VLM group."""
@@ -448,12 +655,30 @@ class VLATrainer(ParamGroup):
         self._refresh_transposes()
         return self.gnorm2.sqrt()
 
+    @staticmethod
+    def _collate(samples):
+        """The one-sample dicts of `step` as the [B, ...] tensors of `forward_backward_batch` (a key must be given by every sample of the group or by none)."""
+        keys = [k for k in samples[0] if samples[0][k] is not None]
+        for smp in samples:
+            if [k for k in smp if smp[k] is not None] != keys:
+                raise ValueError('batch_rows: the samples of one step must carry the same keys')
+        return {k: torch.cat([smp[k] for smp in samples], 0) for k in keys}
+
     def step(self, samples, lr=None, grad_accumulation_steps=1, vlm_lr=None):
         """One optimizer update over `samples` = list of dicts (input_ids, pixel_values, proprios, actions, t, x0 [, position ids]):
         the per-device batch of every accumulation micro-batch, flattened; each sample weighs 1 / len(samples) (the loss is a batch
-        mean, `normalized_loss = loss / grad_accumulation_steps`, train.py:479-498)."""
+        mean, `normalized_loss = loss / grad_accumulation_steps`, train.py:479-498).  With `batch_rows` the samples run in consecutive groups of at
+        most `max_batch` (`plan_row_groups`), each ONE batched pass that weighs len(group) / len(samples)."""
         n = len(samples)
         loss = torch.zeros((), device=self.device)
+        if self.batch_rows:
+            groups = plan_row_groups(n, self.max_batch)
+            for j, (lo, hi, w) in enumerate(groups):
+                first, last = j == 0, j == len(groups) - 1
+                hook = self._exchange_bucket if len(groups) == 1 else (lambda b, w=w, first=first, last=last: self._accumulate_bucket(b, w, first, last))
+                loss = loss + self.forward_backward_batch(on_bucket_ready=hook, **self._collate(samples[lo:hi])) * w
+            gnorm = self.optimizer_step(lr, vlm_lr)
+            return SimpleNamespace(loss=loss, grad_norm=gnorm)
         for j, smp in enumerate(samples):
             first, last = j == 0, j == n - 1
             hook = self._exchange_bucket if n == 1 else (lambda b, first=first, last=last: self._accumulate_bucket(b, 1.0 / n, first, last))
