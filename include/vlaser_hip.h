@@ -277,6 +277,30 @@ int vlaser_chain_down_w8(const void* x, int ldx, const void* W, const float* w_s
  * vlaser_chain_qkv2_supported -- the down projection as two K halves leaving fp32 slabs for q/k/v to fold, measured equal inside the chunk and never shipped --
  * and vlaser_chain_qkv_set_waves, a process-global switch that only that comparison needed.  profiles/HISTORY.md keeps the measurement.) */
 
+/* ---- (ABI 8, additive) co-hosted launches: a prefill launch whose single-round grid leaves CUs idle carries one launch of the action expert's Euler step 0 as EXTRA
+ * WORKGROUPS of its own grid (joint_model.py:140-232: layer l of the action mixture needs the prefix K / V of layer l only, so its first pass can run while the VLM
+ * mixture's layers are still going).  One queue, no flags, no polling: a guest never reads what its host writes, and the launch boundaries order the rest.
+ * A *_cohost entry takes the host's existing arguments plus a guest descriptor and computes exactly what `host; guest` compute, bit for bit: where the dispatcher's choice for
+ * the host, or the guest's shape, has no fused instantiation it launches the host, then the guest, and returns success.  Fused instantiations (B = 1, T = 384, 5 expert rows):
+ *   vlaser_attn_prefill_cohost : attn_prefill<128, 2, 64> + VL_GUEST_CHAIN_QKV        vlaser_gemm_cohost : 64x128 PARTIAL (o_proj) + VL_GUEST_CHAIN_ATTN,
+ *   vlaser_reduce_norm_cohost  : C = 1536 RMS, 3 slabs + VL_GUEST_CHAIN_OPROJ,                               128x256 SWIGLU (gate/up) + VL_GUEST_CHAIN_GU
+ *                                C = 1536 RMS, 7 slabs + VL_GUEST_CHAIN_DOWN
+ * guest == NULL or kind VL_GUEST_NONE: the host alone. */
+enum { VL_GUEST_NONE = 0, VL_GUEST_CHAIN_QKV = 1, VL_GUEST_CHAIN_ATTN = 2, VL_GUEST_CHAIN_OPROJ = 3, VL_GUEST_CHAIN_GU = 4, VL_GUEST_CHAIN_DOWN = 5 };
+typedef struct VlaserCohostGuest {
+  int kind;              /* VL_GUEST_* */
+  const void* args;      /* the guest's existing argument struct: VlaserSkinnyArgs (QKV, OPROJ, GU), VlaserAttnArgs (ATTN), VlaserChainDownArgs (DOWN) */
+} VlaserCohostGuest;
+typedef struct VlaserChainDownArgs {      /* vlaser_chain_down's arguments */
+  const void* x; int ldx; const void* W; const void* res; void* h_out; int M, N, K; unsigned long long* dbg;
+} VlaserChainDownArgs;
+int vlaser_cohost_fused_count(void);            /* launches so far that carried their guest in their own grid (the fallback returns the same 0: this tells them apart) */
+int vlaser_cohost_lab(int mode);                /* timing tools only: 1 = fused kernels run with zero guest workgroups and the guest is skipped (host-alone check); returns the previous mode */
+int vlaser_gemm_cohost(int epi, const VlaserGemmArgs* args, const VlaserCohostGuest* guest, vl_stream_t stream);
+int vlaser_attn_prefill_cohost(const VlaserAttnArgs* args, const VlaserCohostGuest* guest, vl_stream_t stream);
+int vlaser_reduce_norm_cohost(const void* h_in, const float* partials, int n_partials, const void* bias, const void* ls, int norm_kind, const void* norm_w, const void* norm_b,
+                              float eps, void* h_out, void* x_out, int M, int C, const VlaserCohostGuest* guest, vl_stream_t stream);
+
 /* (The two fused layer-step launches measured in r03 / r04 -- o_proj -> gate/up with an in-launch hand-off, +2.0 us in-chain; attention + o_proj in one launch,
  * break-even -- lost to the chain kernels above and left the library in r05 together with include/vlaser_hip_experimental.h: profiles/r03c_euler_fusion.md,
  * profiles/r04i_attn_oproj_timeline.md keep their measurements.) */

@@ -1,0 +1,70 @@
+"""A/B of the co-hosted joint prefill's pairs on ONE model instance (tools/micro/ab_chunk.py builds a model per variant, and two instances of the same variant differ
+by up to 0.06 ms per chunk -- more than a pair is worth).  Every variant = one set of pairs = its own HIP graph over the SAME weights and buffers; rounds replay the
+variants in turn.
+
+    python tools/micro/cohost_ab.py                      # off, all five, each pair alone, each pair left out
+    python tools/micro/cohost_ab.py off qkv+attn all     # named sets
+
+Prints median / min ms per chunk and, against `off` and against `all`, the difference of the medians with the spread of `off` over its rounds."""
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    import bench
+    from vlaser_amd import config as C, synth
+    from vlaser_amd.pizero import COHOST_PAIRS, PiZeroInference
+    names = list(COHOST_PAIRS)
+    variants = sys.argv[1:] or (['off', 'all'] + names + ['+'.join(x for x in names if x != n) for n in names] + ['off'])
+    sets = [None if v == 'off' else tuple(names) if v == 'all' else tuple(v.split('+')) for v in variants]
+    rounds, n = int(os.environ.get('AB_ROUNDS', 9)), 20
+    torch.set_grad_enabled(False)
+    vla = C.VLAConfig(base=C.vlaser_2b())
+    dev = 'cuda:0'
+    sd = synth.vla_state_dict(vla, device=dev, dtype=torch.bfloat16)
+    ids, pv, proprio, noise = bench.make_inputs(vla.base, 1, seed=0)
+    ids_d, pv_d, pro_d, noise_d = ids.to(dev), pv.to(dev).to(torch.bfloat16), proprio.to(dev), noise.to(dev)
+    valid = (ids != vla.base.pad_token_id).sum(-1).to(dev)
+    m = PiZeroInference(vla, device=dev, max_batch=1, euler_opts='qkv16,gu16,glue1,chain,cohost')
+    m.load_state_dict(sd)
+    call = lambda: m.infer_action(ids_d, pv_d, proprios=pro_d, noise=noise_d, valid_len=valid)
+    graphs, ref = [], None
+    for v, s in zip(variants, sets):
+        m.cohost_pairs, m._graphs = s, {}
+        for _ in range(3):
+            o = call()
+        torch.cuda.synchronize()
+        graphs.append(m._graphs)
+        ref = o.clone() if ref is None else ref
+        assert torch.equal(o, ref), f'variant {v}: the chunk differs'
+    times = [[] for _ in variants]
+    for r in range(rounds):
+        for i, s in enumerate(sets):
+            m.cohost_pairs, m._graphs = s, graphs[i]
+            call()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                call()
+            torch.cuda.synchronize()
+            times[i].append((time.perf_counter() - t0) / n * 1e3)
+    med = lambda ts: sorted(ts)[len(ts) // 2]
+    off = [ts for v, ts in zip(variants, times) if v == 'off']
+    spread = max(max(ts) - min(ts) for ts in off) if off else float('nan')
+    m_off = med(off[0]) if off else float('nan')
+    m_all = next((med(ts) for v, ts in zip(variants, times) if v == 'all'), float('nan'))
+    print(f'one model instance, {rounds} rounds x {n} chunks per variant; spread of `off` over its rounds {spread:.3f} ms; all chunks bit-identical\n')
+    print('| pairs on | median ms/chunk | min | max | - off | - all |')
+    print('|---|---|---|---|---|---|')
+    for v, ts in zip(variants, times):
+        print(f'| `{v}` | {med(ts):.3f} | {min(ts):.3f} | {max(ts):.3f} | {med(ts) - m_off:+.3f} | {med(ts) - m_all:+.3f} |')
+
+
+if __name__ == '__main__':
+    main()

@@ -37,6 +37,15 @@ class SkinnyArgs(C.Structure):
                 ('attn_splits', i32), ('attn_group', i32), ('attn_nq', i32), ('dbg', vp), ('w_scale', vp)]
 
 
+class CohostGuest(C.Structure):
+    """The guest of a co-hosted launch (include/vlaser_hip.h): kind = GUEST_*, args = address of the guest's own argument struct (kept alive by the caller)."""
+    _fields_ = [('kind', i32), ('args', vp)]
+
+
+class ChainDownArgs(C.Structure):
+    _fields_ = [('x', vp), ('ldx', i32), ('W', vp), ('res', vp), ('h_out', vp), ('M', i32), ('N', i32), ('K', i32), ('dbg', vp)]
+
+
 class VlaStageArgs(C.Structure):
     _fields_ = [('ids', vp), ('ids_out', vp), ('B', i32), ('T', i32), ('pad_id', i64), ('valid_in', vp), ('valid_is_i64', i32), ('valid_out', vp),
                 ('proprio', vp), ('proprio_out', vp), ('n_proprio', i32), ('noise', vp), ('noise_out', vp), ('n_noise', i32),
@@ -50,11 +59,17 @@ class VlaStageArgs(C.Structure):
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_LS_RES, EPI_RES, EPI_SWIGLU, EPI_QKV_ROPE, EPI_VIT_QKV, EPI_F32, EPI_PARTIAL, EPI_SWIGLU_BWD = range(11)
 ATTN_FULL, ATTN_CAUSAL, ATTN_PREFIX, ATTN_DENSE = range(4)
 PRO_PLAIN, PRO_NORM, PRO_ATTN = range(3)
+GUEST_NONE, GUEST_CHAIN_QKV, GUEST_CHAIN_ATTN, GUEST_CHAIN_OPROJ, GUEST_CHAIN_GU, GUEST_CHAIN_DOWN = range(6)
 SK_PARTIAL, SK_QKV_ROPE, SK_SWIGLU, SK_F32, SK_BIAS, SK_BIAS_SILU = range(6)
 
 _SIGS = {
     'vlaser_gemm': [i32, C.POINTER(GemmArgs), vp],
     'vlaser_gemm_nn': [i32, C.POINTER(GemmArgs), vp],
+    'vlaser_cohost_lab': [i32],
+    'vlaser_cohost_fused_count': [],
+    'vlaser_gemm_cohost': [i32, C.POINTER(GemmArgs), C.POINTER(CohostGuest), vp],
+    'vlaser_attn_prefill_cohost': [C.POINTER(AttnArgs), C.POINTER(CohostGuest), vp],
+    'vlaser_reduce_norm_cohost': [vp, vp, i32, vp, vp, i32, vp, vp, f32, vp, vp, i32, i32, C.POINTER(CohostGuest), vp],
     'vlaser_set_cu_budget': [i32],
     'vlaser_get_cu_budget': [],
     'vlaser_stream_create_cumask': [i32, i32, C.POINTER(vp)],

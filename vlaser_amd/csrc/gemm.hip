@@ -12,6 +12,7 @@
 // blockIdx is remapped so each XCD owns a contiguous run of tiles that share the same weight panel (guide T1).
 
 #include "common.h"
+#include "chain_kernels.h"
 #include "../../include/vlaser_hip.h"
 
 #define BN 128
@@ -814,242 +815,49 @@ __device__ __forceinline__ bf16x8 tile_frag(const char* tile, int c0, int ks, in
 // retired by an explicit lgkmcnt(0) in front of the barrier -- long complete by then -- so no prefetch depth is lost (r02's version of the idea moved the barrier and lost a stage).
 template <int EPI, int BM, int BNT, int WM, int WN, int NST, bool WKM = false, bool AKM = false, bool IFIRST = GLDS_ISSUE_FIRST != 0, bool ASYM = false, bool SPREAD = false,
           bool PIPE = false>
+__device__ __forceinline__ void gemm_glds_body(const GemmP& p, const int bx, const int gx) {      // bx of gx: the workgroup's place in the launch's x extent (a co-hosted launch's grid is longer)
+#define VL_WG_X bx
+#define VL_WG_Y blockIdx.y
+#define VL_WG_Z blockIdx.z
+#define VL_GRID_X gx
+#define VL_GRID_Y gridDim.y
+#include "gemm_glds.inc"
+#undef VL_WG_X
+#undef VL_WG_Y
+#undef VL_WG_Z
+#undef VL_GRID_X
+#undef VL_GRID_Y
+}
+
+template <int EPI, int BM, int BNT, int WM, int WN, int NST, bool WKM = false, bool AKM = false, bool IFIRST = GLDS_ISSUE_FIRST != 0, bool ASYM = false, bool SPREAD = false,
+          bool PIPE = false>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmP p) {
-  static_assert(!PIPE || !IFIRST, "PIPE: the refill is spread or issued behind the first read block");
-  constexpr int NW = WM * WN;
-  constexpr int WTM = BM / WM, WTN = BNT / WN;
-  constexpr int MT = WTM / 16, NT = WTN / 16;
-  constexpr int STAGE = (BM + BNT) * 128;               // bytes: A tile | W tile (row-major, 128 B = 64 k per row)
-  constexpr int NPA = BM / 8, NPW = BNT / 8;             // 1 KiB (8-row) pieces of the A / W tile (WKM: 64 k-rows x 2 BNT bytes = the same count)
-  constexpr int WROWB = BNT * 2, WRPP = 1024 / WROWB, WSPR = BNT / 8;      // WKM: bytes per k-row, k-rows per piece, 16-byte slots per k-row
-  constexpr int AROWB = BM * 2, ARPP = 1024 / AROWB, ASPR = BM / 8;        // AKM: the same for the A tile
-  static_assert(!AKM || (WKM && (BM == 128 || BM == 256)), "AKM needs WKM and a power-of-two tile of >= 16 slots per k-row");
-  constexpr int PA = (NPA + NW - 1) / NW, PW = (NPW + NW - 1) / NW;     // pieces per wave per K-tile; an uneven split re-issues the last piece
-  constexpr int PIECES = PA + PW;                        // (same bytes to the same LDS address: benign) so every wave's vmcnt arithmetic is identical
-  static_assert(NPA * 8 == BM && NPW * 8 == BNT, "tile rows must be multiples of 8");
-  static_assert(NT % 2 == 0, "fused pair epilogues need an even number of 16-column tiles per wave");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const VlaserGemmArgs& a = p.a;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave / WN, wc = wave % WN;
-  GEMM_STAMP(0)
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile_m = bid % p.tiles_m, tile_n = bid / p.tiles_m;
-  const int m0 = tile_m * BM, n0 = tile_n * BNT;
-  const int kc = a.K / (int)gridDim.y;
-  const int kbase = blockIdx.y * kc;
-  const int bz = blockIdx.z;
-  const bf16_t* A = reinterpret_cast<const bf16_t*>(a.A) + (size_t)bz * a.a_bs;
-  const bf16_t* W = reinterpret_cast<const bf16_t*>(a.W) + (size_t)(a.w_group > 1 ? bz / a.w_group : bz) * a.w_bs;
-  const int nk = kc / BK;
+#define VL_WG_X blockIdx.x
+#define VL_WG_Y blockIdx.y
+#define VL_WG_Z blockIdx.z
+#define VL_GRID_X gridDim.x
+#define VL_GRID_Y gridDim.y
+#include "gemm_glds.inc"
+#undef VL_WG_X
+#undef VL_WG_Y
+#undef VL_WG_Z
+#undef VL_GRID_X
+#undef VL_GRID_Y
+}
 
-  // per-lane source pointers of this wave's pieces (row clamped; the swizzle lives in the source slot)
-  const int prow = lane >> 3, pslot = lane & 7;
-  const bf16_t* srcA[PA];
-  const bf16_t* srcW[PW];
-#pragma unroll
-  for (int i = 0; i < PA; ++i) {
-    if constexpr (AKM) {
-      const int krow = min(wave * PA + i, NPA - 1) * ARPP + lane / ASPR;
-      const int slot = (lane % ASPR) ^ (2 * ((krow & 3) | (((krow >> 3) & 1) << 2)));
-      srcA[i] = A + (size_t)(kbase + krow) * a.lda + min(m0 + slot * 8, ((a.M + 7) & ~7) - 8);
-    } else {
-      const int row = min(wave * PA + i, NPA - 1) * 8 + prow;
-      srcA[i] = A + (size_t)min(m0 + row, a.M - 1) * a.lda + kbase + ((pslot ^ (row & 7)) << 3);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < PW; ++i) {
-    if constexpr (WKM) {
-      const int krow = min(wave * PW + i, NPW - 1) * WRPP + lane / WSPR;              // k-row of this lane inside the tile
-      const int slot = (lane % WSPR) ^ (2 * ((krow & 3) | (((krow >> 3) & 1) << 2)));    // logical 16-byte slot fetched into physical slot lane % WSPR
-      srcW[i] = W + (size_t)(kbase + krow) * a.ldw + min(n0 + slot * 8, ((a.N + 7) & ~7) - 8);   // columns past N (chunk-aligned clamp) only feed dropped outputs
-    } else {
-      const int row = min(wave * PW + i, NPW - 1) * 8 + prow;
-      srcW[i] = W + (size_t)min(n0 + row, a.N - 1) * a.ldw + kbase + ((pslot ^ (row & 7)) << 3);
-    }
-  }
-  const uint32_t lds0 = (uint32_t)(uintptr_t)smem;      // LDS byte address of the stage ring (low 32 bits of the generic pointer)
-  constexpr int WRING = ASYM ? NST * BM * 128 : 0;      // ASYM: [NST A stages][NST + 1 W stages]; else [NST (A | W) stages]
-  // the only place that turns a piece into a source address and an LDS destination: piece i of this wave's PA (PW) pieces of the A (W) tile at K offset ko into the stage at `base`
-  auto k_off = [&](int kt) { return min(kt, nk - 1) * BK; };      // tiles past the end re-fetch the last one (never read)
-  auto a_stage = [&](int sa) { return lds0 + sa * (ASYM ? BM * 128 : STAGE); };
-  auto w_stage = [&](int sw2) { return ASYM ? lds0 + WRING + sw2 * (BNT * 128) : lds0 + sw2 * STAGE + BM * 128; };
-  auto piece_a = [&](int i, int ko, uint32_t base) { glds16(srcA[i] + (AKM ? (size_t)ko * a.lda : (size_t)ko), __builtin_amdgcn_readfirstlane(base + min(wave * PA + i, NPA - 1) * 1024)); };
-  auto piece_w = [&](int i, int ko, uint32_t base) { glds16(srcW[i] + (WKM ? (size_t)ko * a.ldw : (size_t)ko), __builtin_amdgcn_readfirstlane(base + min(wave * PW + i, NPW - 1) * 1024)); };
-  // piece j of the PIECES of a refill (A pieces first, then W: the order the vmcnt arithmetic assumes): A tile kta into A stage sa, W tile ktw into W stage sw2
-  auto issue_piece = [&](int j, int kta, int sa, int ktw, int sw2) {
-    if (j < PA) piece_a(j, k_off(kta), a_stage(sa));
-    else piece_w(j - PA, k_off(ktw), w_stage(sw2));
-  };
-  auto issue_a = [&](int kt, int sa) {
-    const int ko = k_off(kt);
-    const uint32_t base = a_stage(sa);
-#pragma unroll
-    for (int i = 0; i < PA; ++i) piece_a(i, ko, base);
-  };
-  auto issue_w = [&](int kt, int sw2) {
-    const int ko = k_off(kt);
-    const uint32_t base = w_stage(sw2);
-#pragma unroll
-    for (int i = 0; i < PW; ++i) piece_w(i, ko, base);
-  };
-  auto issue_tile = [&](int kt, int st) { issue_a(kt, st); issue_w(kt, st); };
-  // the refill of step kt as one burst: the stage(s) read in step kt - 1 (stn; ASYM: A stage stn, W stage swn) take the tiles NST - 1 (ASYM, W: NST) ahead.  (The
-  // arguments by reference and the two call sites of the plain loop are the form that leaves every kernel's register allocation where it was: profiles/gemm_dedup_ab.md.)
-  auto refill = [&](const int& kt, const int& stn, const int& swn) {
-    if constexpr (ASYM) { issue_a(kt + NST - 1, stn); issue_w(kt + NST, swn); }
-    else issue_tile(kt + NST - 1, stn);
-  };
-
-  f32x4 acc[NT][MT];
-#pragma unroll
-  for (int i = 0; i < NT; ++i)
-#pragma unroll
-    for (int j = 0; j < MT; ++j) acc[i][j] = f32x4{0, 0, 0, 0};
-
-#pragma unroll
-  for (int st = 0; st < NST - 1; ++st) issue_tile(st, st);
-  if constexpr (ASYM) issue_w(NST - 1, NST - 1);
-  GEMM_STAMP(1)
-  const int fr = lane & 15, fq = lane >> 4;
-  int st = 0;                                            // stage of tile kt (ASYM: of its A tile)
-  [[maybe_unused]] int sw = 0;                           // ASYM: stage of tile kt's W tile (ring of NST + 1)
-  if constexpr (PIPE) {
-    auto read_frags = [&](int ks, const char* As, const char* Ws, bf16x8 (&fa)[MT], bf16x8 (&fw)[NT]) __attribute__((always_inline)) {
-#pragma unroll
-      for (int t = 0; t < MT; ++t) fa[t] = tile_frag<AKM ? AROWB : 0>(As, wr * WTM + t * 16, ks, fr, fq);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) fw[t] = tile_frag<WKM ? WROWB : 0>(Ws, wc * WTN + t * 16, ks, fr, fq);
-    };
-    // one block of MT x NT MFMAs; `blk` = 0 / 1: first / second block of the step (the spread refill counts MFMAs over both); kt / stn / swn: the step whose refill rides here
-    auto mfma_block = [&](const bf16x8 (&fa)[MT], const bf16x8 (&fw)[NT], int blk, bool refill, int kt, int stn, int swn) __attribute__((always_inline)) {
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          acc[nt][mt] = mfma16(fw[nt], fa[mt], acc[nt][mt]);
-          if constexpr (SPREAD) {
-            constexpr int GAP = (2 * MT * NT) / (PIECES + 1) > 0 ? (2 * MT * NT) / (PIECES + 1) : 1;
-            const int g = blk * (MT * NT) + nt * MT + mt + 1;
-            if (refill && g % GAP == 0 && g / GAP - 1 < PIECES) {
-              __builtin_amdgcn_sched_barrier(0);
-              issue_piece(g / GAP - 1, kt + NST - 1, stn, ASYM ? kt + NST : kt + NST - 1, ASYM ? swn : stn);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          }
-        }
-    };
-    bf16x8 faA[MT], fwA[NT], faB[MT], fwB[NT];
-    for (int kt = 0; kt < nk; ++kt) {
-      if constexpr (ASYM) wait_vmcnt<PA * (NST - 2) + PW * (NST - 1)>();
-      else wait_vmcnt<PIECES * (NST - 2)>();               // this wave's pieces of tile kt have landed (younger tiles may fly)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // set B's reads of tile kt-1 (issued a whole MFMA block ago) are retired: stage kt-1 may be refilled behind the barrier
-      __builtin_amdgcn_s_barrier();
-      GEMM_STAMP(2 + kt)
-      int stn = st + NST - 1; if (stn >= NST) stn -= NST;
-      [[maybe_unused]] int swn = sw + NST; if (swn >= NST + 1) swn -= NST + 1;
-      const char* As = smem + st * (ASYM ? BM * 128 : STAGE);
-      const char* Ws = ASYM ? smem + WRING + sw * (BNT * 128) : As + BM * 128;
-      read_frags(0, As, Ws, faA, fwA);
-      // the refill of this step: spread over the step's two MFMA blocks, or -- burst form, and ALWAYS in step 0, which has no first block -- in one piece behind the first read
-      // block, in the order the vmcnt arithmetic assumes (A pieces, then W pieces)
-      if (!SPREAD || kt == 0) refill(kt, stn, swn);
-      if (kt > 0) mfma_block(faB, fwB, 0, SPREAD, kt, stn, swn);
-      read_frags(1, As, Ws, faB, fwB);
-      mfma_block(faA, fwA, 1, SPREAD && kt > 0, kt, stn, swn);
-      if (++st == NST) st = 0;
-      if constexpr (ASYM) { if (++sw == NST + 1) sw = 0; }
-    }
-    mfma_block(faB, fwB, 0, false, 0, 0, 0);               // (nk - 1, h1)
-  } else
-  {
-  for (int kt = 0; kt < nk; ++kt) {
-    if constexpr (ASYM) wait_vmcnt<PA * (NST - 2) + PW * (NST - 1)>();
-    else wait_vmcnt<PIECES * (NST - 2)>();               // this wave's pieces of tile kt have landed (younger tiles may fly)
-    __builtin_amdgcn_s_barrier();                        // ... and everyone else's; also: all waves are done reading stage kt-1
-    GEMM_STAMP(2 + kt)
-    int stn = st + NST - 1; if (stn >= NST) stn -= NST;  // = (kt-1) % NST: the stage read in the previous step
-    const char* As = smem + st * (ASYM ? BM * 128 : STAGE);
-    const char* Ws = ASYM ? smem + WRING + sw * (BNT * 128) : As + BM * 128;
-    [[maybe_unused]] int swn = sw + NST; if (swn >= NST + 1) swn -= NST + 1;      // ASYM: = (kt - 1) % (NST + 1): the W stage read in the previous step
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 fa[MT], fw[NT];
-      // (r03) the refill of stage kt-1 is issued BEHIND the first half's fragment reads: an LDS-DMA piece costs ~100-185 issue cycles
-      // (MI355X_MICROARCH.md), and in front of the reads the whole K-step sat behind PIECES of them before its first ds_read went out
-      if constexpr (!SPREAD) {
-        if (ks == 1 && !IFIRST) refill(kt, stn, swn);
-        if (ks == 0 && IFIRST) refill(kt, stn, swn);
-      }
-#pragma unroll
-      for (int t = 0; t < MT; ++t) fa[t] = tile_frag<AKM ? AROWB : 0>(As, wr * WTM + t * 16, ks, fr, fq);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) fw[t] = tile_frag<WKM ? WROWB : 0>(Ws, wc * WTN + t * 16, ks, fr, fq);
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          acc[nt][mt] = mfma16(fw[nt], fa[mt], acc[nt][mt]);
-          if constexpr (SPREAD) {
-            constexpr int GAP = (2 * MT * NT) / (PIECES + 1) > 0 ? (2 * MT * NT) / (PIECES + 1) : 1;
-            const int g = ks * (MT * NT) + nt * MT + mt + 1;          // MFMAs of this K-step issued so far (a compile-time value after unrolling)
-            if (g % GAP == 0 && g / GAP - 1 < PIECES) {
-              __builtin_amdgcn_sched_barrier(0);
-              issue_piece(g / GAP - 1, kt + NST - 1, stn, ASYM ? kt + NST : kt + NST - 1, ASYM ? swn : stn);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          }
-        }
-    }
-    if (++st == NST) st = 0;
-    if constexpr (ASYM) { if (++sw == NST + 1) sw = 0; }
-  }
-  }
-  GEMM_STAMP(36)
-  wait_vmcnt<0>();                                       // drain the clamped look-ahead tiles before the block retires
-
-  VlaserGemmArgs ea = a;      // batched: shift the output (bf16 / fp32 / partial) of this batch element
-  if (bz > 0) {
-    if (ea.out) ea.out = reinterpret_cast<char*>(ea.out) + (size_t)bz * a.o_bs * (EPI == VL_EPI_F32 ? 4 : 2);
-    if (ea.out_f32) ea.out_f32 += (size_t)bz * a.o_bs;
-    if (ea.res) ea.res = reinterpret_cast<const char*>(ea.res) + (size_t)bz * a.o_bs * 2;
-  }
-  [[maybe_unused]] char* scr = nullptr;                // this wave's scratch for the row-contiguous stores: the stage ring, once every wave is out of the K loop
-  if constexpr (EPI == VL_EPI_NONE || EPI == VL_EPI_BIAS || EPI == VL_EPI_BIAS_GELU || EPI == VL_EPI_BIAS_LS_RES || EPI == VL_EPI_RES) {
-    static_assert(NW * EpiScratch<MT, NT>::BYTES <= NST * STAGE + (ASYM ? BNT * 128 : 0), "epilogue scratch exceeds the stage ring");
-    __builtin_amdgcn_s_barrier();                        // (each wave drained its own LDS-DMA pieces above: nothing lands in the ring any more)
-    scr = smem + wave * EpiScratch<MT, NT>::BYTES;
-  }
-  GEMM_STAMP(37)
-  if constexpr (EPI == VL_EPI_NONE && AKM) {           // the weight-gradient form: optionally this wave's share of the gradient norm (one slot per wave,
-    const float ssq = epilogue_tile<EPI, MT, NT, true>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc, scr);
-    if (a.sumsq_part) {
-      const float w = wave_sum(ssq);
-      if (lane == 0) a.sumsq_part[(size_t)(blockIdx.x + gridDim.x * blockIdx.z) * NW + wave] = w;
-    }
+// Co-hosted launch (csrc/chain_kernels.h): the host's grid, its x extent lengthened by the guest's workgroups.  Workgroups bx < host_grid are the GEMM's (tile index and
+// XCD remap over host_grid, NOT gridDim.x); the rest run guest workgroup (bx - host_grid) * gridDim.y + blockIdx.y -- the split-K copies of the appended x range all
+// carry guest work.  Block = the host's; dynamic LDS = the larger request (both hosts built here ask for > 80 KB: one workgroup per CU, a guest only lands on a CU
+// the host left idle or has already left).
+template <class G, int EPI, int BM, int BNT, int WM, int WN, int NST, bool WKM, bool AKM, bool IFIRST, bool ASYM, bool SPREAD, bool PIPE>
+__global__ __launch_bounds__(WM * WN * 64) void gemm_glds_cohost_kernel(GemmP p, typename G::P gp, int host_grid) {
+  static_assert(G::THREADS <= WM * WN * 64, "the guest's block must fit the host's");
+  if ((int)blockIdx.x < host_grid) {
+    gemm_glds_body<EPI, BM, BNT, WM, WN, NST, WKM, AKM, IFIRST, ASYM, SPREAD, PIPE>(p, blockIdx.x, host_grid);
   } else {
-    if constexpr (EPI == VL_EPI_SWIGLU) {                // 16-byte stores where the tile allows them
-      if (epilogue_tile_swiglu<MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc)) {
-        GEMM_STAMP(38)
-        return;
-      }
-    }
-    if (!tile_epilogue<EPI, MT, NT>(ea, m0 + wr * WTM, n0 + wc * WTN, fr, fq, acc, scr)) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const int m = m0 + wr * WTM + mt * 16 + fr;
-        if constexpr (EPI == VL_EPI_SWIGLU) {
-#pragma unroll
-          for (int nt = 0; nt < NT; nt += 2) epilogue<EPI>(ea, m, n0 + wc * WTN + nt * 16 + fq * 4, acc[nt][mt], acc[nt + 1][mt]);
-        } else {
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt) epilogue<EPI>(ea, m, n0 + wc * WTN + nt * 16 + fq * 4, acc[nt][mt], acc[nt][mt]);
-        }
-      }
-    }
+    if constexpr (G::THREADS < WM * WN * 64) { if ((int)threadIdx.x >= G::THREADS) return; }
+    G::run(gp, ((int)blockIdx.x - host_grid) * (int)gridDim.y + (int)blockIdx.y);
   }
-  GEMM_STAMP(38)
 }
 
 // ---------------------------------------------------------------------------------------------- TN form, two staggered wave groups (r04)
@@ -1201,6 +1009,32 @@ static int launch_glds(const VlaserGemmArgs* args, hipStream_t stream, int split
   return 0;
 }
 
+// the co-hosted form: guest_wgs workgroups of guest G (its parameters gp, its dynamic LDS guest_lds) behind the host's tiles, batch 1
+template <class G, int EPI, int BM, int BNT, int WM, int WN, int NST, int FLAGS>
+static int launch_glds_cohost(const VlaserGemmArgs* args, hipStream_t stream, int splits, const typename G::P& gp, int guest_wgs, int guest_lds) {      // (splits > 1: G bounds-checks its index)
+  constexpr bool ASYM_ = (FLAGS & ASYM) != 0;
+  constexpr auto kernel = gemm_glds_cohost_kernel<G, EPI, BM, BNT, WM, WN, NST, false, false, (FLAGS & IFIRST) != 0 || (FLAGS == 0 && GLDS_ISSUE_FIRST != 0), ASYM_, (FLAGS & SPREAD) != 0, (FLAGS & PIPE) != 0>;
+  GemmP p;
+  p.a = *args;
+  p.tiles_m = (args->M + BM - 1) / BM;
+  p.tiles_n = (args->N + BNT - 1) / BNT;
+  constexpr int host_lds = NST * (BM + BNT) * 128 + (ASYM_ ? BNT * 128 : 0);
+  static_assert(host_lds > 80 * 1024 && host_lds <= 160 * 1024, "a co-hosting GEMM keeps its CU to itself");
+  const int lds = guest_lds > host_lds ? guest_lds : host_lds;
+  VL_CHECK(lds <= 160 * 1024, "co-hosted GEMM: the guest asks for %d bytes of LDS", guest_lds);
+  const int host_grid = p.tiles_m * p.tiles_n;
+  if (int rc = set_max_lds_once(kernel, lds)) return rc;
+  if (vl_cohost_lab_zero_guests()) guest_wgs = 0;
+  // with K-splits in y the workgroups are numbered x + y * gridDim.x, and xcd_remap takes bx % 8 for the XCD: the lengthened x extent stays a multiple of 8, as the
+  // host's own is, so that every y slice starts on XCD 0 (the guest bounds-checks its index)
+  int gx = host_grid + (guest_wgs + splits - 1) / splits;
+  if (splits > 1 && host_grid % 8 == 0) gx = (gx + 7) & ~7;
+  hipLaunchKernelGGL(kernel, dim3(gx, splits, 1), dim3(WM * WN * 64), lds, stream, p, gp, host_grid);
+  VL_LAUNCH_CHECK();
+  vl_cohost_count_fused();
+  return 0;
+}
+
 template <int EPI, int BM>
 static int launch_bm(const VlaserGemmArgs* args, hipStream_t stream, int splits) {
   GemmP p;
@@ -1231,8 +1065,9 @@ extern "C" int vlaser_get_cu_budget(void) { return g_cu_budget; }
 // first losing to smallest: 64x128 (8 waves, 4 stages) for the smallest problems, then 128x128 (4 stages), 128x256 (3 stages),
 // 256x256 (2 stages).  Multi-round grids take the configuration with the least modelled time (rounds x tile area / measured
 // rate); <= 32 activation rows stay on the 32-row register-staged kernel (a 64-row tile would be 50+ % padding).
+// guest / hosted: a co-hosted call (vlaser_gemm_cohost).  *hosted = 1 when the launch carried the guest; otherwise the caller launches it behind this one.
 template <int EPI, bool WKM = false, bool AKM = false>
-static int launch(const VlaserGemmArgs* args, hipStream_t stream) {
+static int launch(const VlaserGemmArgs* args, hipStream_t stream, const VlaserCohostGuest* guest = nullptr, int* hosted = nullptr) {
   const int splits = (EPI == VL_EPI_PARTIAL && args->k_splits > 1) ? args->k_splits : 1;
   const int tn = (args->N + BN - 1) / BN;
   const int nb = args->batch > 1 ? args->batch : 1;
@@ -1293,6 +1128,26 @@ static int launch(const VlaserGemmArgs* args, hipStream_t stream) {
     }
     vlaser_set_error("vlaser_gemm_tn_lds: force_cfg = %d is not a configuration code of the TN form (see the table at force_bm in include/vlaser_hip.h)", bm);
     return -1;
+  }
+  if constexpr (!WKM && !AKM && (EPI == VL_EPI_SWIGLU || EPI == VL_EPI_PARTIAL)) {
+    // the two fused instantiations: the joint prefill's gate/up (128x256, 210 of 256 CUs) with the expert's gate/up, its o_proj (64x128, 3 K-splits, 216 CUs) with the expert's attention
+    if (guest && hosted && nb == 1) {
+      if constexpr (EPI == VL_EPI_SWIGLU) {
+        ChainGuP gp; int wgs, lds;
+        if (bm == 1200 && vl_cohost_chain_gu(guest, &gp, &wgs, &lds)) {
+          *hosted = 1;
+          return launch_glds_cohost<GuestChainGu, EPI, 128, 256, 2, 4, 3, SPREAD>(args, stream, splits, gp, wgs, lds);
+        }
+      } else {
+        ChainAttnP gp; int waves;
+        if (bm == 1500 && vl_cohost_chain_attn(guest, &gp, &waves)) {
+          *hosted = 1;
+          // one wave per guest workgroup, as in the stand-alone launch (28 waves on 28 of the 40 idle CUs): eight to a CU pulled 256 KB of K / V^T through one CU and
+          // outlasted the host (measured: profiles/cohost_ab.md)
+          return launch_glds_cohost<GuestChainAttn, EPI, 64, 128, 2, 4, 4, SPREAD | PIPE>(args, stream, splits, gp, waves, 0);
+        }
+      }
+    }
   }
   switch (bm) {
     // r05: the refill's pieces go out one at a time between the K-step's MFMAs (SPREAD: bit-identical, -1 ... -9 % per launch, tools/micro/spread_lab.py); 1101 / 1201 / 1304 / 1441 /
@@ -1552,7 +1407,7 @@ extern "C" int vlaser_gemm_tn_lds(const void* At, const void* Wt, void* out, int
   return launch<VL_EPI_NONE, true, true>(&a, reinterpret_cast<hipStream_t>(s));
 }
 
-extern "C" int vlaser_gemm(int epi, const VlaserGemmArgs* a, vl_stream_t s) {
+static int gemm_entry(int epi, const VlaserGemmArgs* a, const VlaserCohostGuest* guest, int* hosted, vl_stream_t s) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(s);
   VL_CHECK(a && a->A && a->W, "vlaser_gemm: null operand");
   VL_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "vlaser_gemm: bad shape M=%d N=%d K=%d", a->M, a->N, a->K);
@@ -1575,7 +1430,7 @@ extern "C" int vlaser_gemm(int epi, const VlaserGemmArgs* a, vl_stream_t s) {
     case VL_EPI_PARTIAL:
       VL_CHECK(a->out_f32 && a->N % 4 == 0, "partial: out_f32 null or N %% 4 != 0");
       VL_CHECK(a->k_splits >= 1 && a->K % (a->k_splits * BK) == 0, "partial: K=%d not divisible by k_splits*64 (k_splits=%d)", a->K, a->k_splits);
-      return launch<VL_EPI_PARTIAL>(a, stream);
+      return launch<VL_EPI_PARTIAL>(a, stream, guest, hosted);
     case VL_EPI_BIAS: VL_CHECK(a->out && a->bias, "out/bias null"); return launch<VL_EPI_BIAS>(a, stream);
     case VL_EPI_BIAS_GELU: VL_CHECK(a->out && a->bias, "out/bias null"); return launch<VL_EPI_BIAS_GELU>(a, stream);
     case VL_EPI_BIAS_LS_RES:
@@ -1584,7 +1439,7 @@ extern "C" int vlaser_gemm(int epi, const VlaserGemmArgs* a, vl_stream_t s) {
     case VL_EPI_RES: VL_CHECK(a->out && a->res, "out/res null"); return launch<VL_EPI_RES>(a, stream);
     case VL_EPI_SWIGLU:
       VL_CHECK(a->out && a->N % 32 == 0 && a->ldo % 4 == 0, "swiglu: N must be a multiple of 32, ldo of 4");
-      return launch<VL_EPI_SWIGLU>(a, stream);
+      return launch<VL_EPI_SWIGLU>(a, stream, guest, hosted);
     case VL_EPI_QKV_ROPE:
       VL_CHECK(a->q_out && a->k_cache && a->vt_cache && a->rope_cos && a->rope_sin && a->pos_ids && a->bias, "qkv_rope: null pointer");
       VL_CHECK(a->N == (a->n_q_heads + 2 * a->n_kv_heads) * 128, "qkv_rope: N mismatch");
@@ -1596,6 +1451,13 @@ extern "C" int vlaser_gemm(int epi, const VlaserGemmArgs* a, vl_stream_t s) {
       return launch<VL_EPI_VIT_QKV>(a, stream);
     default: vlaser_set_error("vlaser_gemm: unknown epilogue %d", epi); return -1;
   }
+}
+extern "C" int vlaser_gemm(int epi, const VlaserGemmArgs* a, vl_stream_t s) { return gemm_entry(epi, a, nullptr, nullptr, s); }
+/* vlaser_gemm + a guest launch (include/vlaser_hip.h, co-hosted launches): fused where the dispatcher's tile and the guest's shape have an instantiation, host then guest otherwise */
+extern "C" int vlaser_gemm_cohost(int epi, const VlaserGemmArgs* a, const VlaserCohostGuest* guest, vl_stream_t s) {
+  int hosted = 0;
+  if (int rc = gemm_entry(epi, a, guest, &hosted, s)) return rc;
+  return hosted ? 0 : vl_cohost_guest_launch(guest, s);
 }
 
 // out[M,N] = A[M,K] @ B[K,N] with B row-major ("k-major": a forward weight [N_out, K_in] read as the B of its own dgrad dX = dY @ W);

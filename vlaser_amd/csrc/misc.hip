@@ -3,6 +3,7 @@
 // (time embedding, action encoder input, final norm + action decoder + Euler update).
 // All are one-wave-per-row or one-block kernels with 16-byte vector accesses and fp32 statistics.
 #include "common.h"
+#include "chain_kernels.h"
 #include "../../include/vlaser_hip.h"
 
 // ---------------------------------------------------------------------------------------------- LayerNorm / RMSNorm
@@ -1249,89 +1250,68 @@ __global__ __launch_bounds__(64) void reduce_norm_kernel(const bf16_t* __restric
 // kernel above walks the row's 512-column chunks behind `c < C` / `if (ptr)` branches, i.e. one L2 round trip per chunk plus one
 // more for the norm weights after the statistics: 6.5-8.3 us per launch on the path's seams against 4.x us here.
 template <int NORM, int NCH, int SX, bool BL>
+__device__ __forceinline__ void reduce_norm_exact_body(const bf16_t* __restrict__ h_in, const float* __restrict__ partials,
+                                                       const bf16_t* __restrict__ bias, const bf16_t* __restrict__ ls,
+                                                       const bf16_t* __restrict__ nw, const bf16_t* __restrict__ nb, float eps,
+                                                       bf16_t* __restrict__ h_out, bf16_t* __restrict__ x_out, int M, const int row_) {      // one wave = one row, row_
+#define VL_WG_X row_
+#define VL_WG_Y 0
+#define VL_WG_Z 0
+#define VL_GRID_X 1
+#define VL_GRID_Y 1
+#include "reduce_norm_exact.inc"
+#undef VL_WG_X
+#undef VL_WG_Y
+#undef VL_WG_Z
+#undef VL_GRID_X
+#undef VL_GRID_Y
+}
+template <int NORM, int NCH, int SX, bool BL>
 __global__ __launch_bounds__(64) void reduce_norm_exact_kernel(const bf16_t* __restrict__ h_in, const float* __restrict__ partials,
                                                                 const bf16_t* __restrict__ bias, const bf16_t* __restrict__ ls,
                                                                 const bf16_t* __restrict__ nw, const bf16_t* __restrict__ nb, float eps,
                                                                 bf16_t* __restrict__ h_out, bf16_t* __restrict__ x_out, int M) {
-  constexpr int C = NCH * 512;
-  const int lane = threadIdx.x & 63, row = blockIdx.x;
-  const size_t slab = (size_t)M * C;
-  f32x4 q[NCH][2 * SX];
-  u32x4 hi[NCH], bv[NCH], lv[NCH], wv[NCH], nbv[NCH];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    const int c = (lane + 64 * i) * 8;
-    const size_t off = (size_t)row * C + c;
-#pragma unroll
-    for (int u = 0; u < SX; ++u) {
-      const float* pp = partials + off + (size_t)u * slab;
-      q[i][2 * u] = *reinterpret_cast<const f32x4*>(pp);
-      q[i][2 * u + 1] = *reinterpret_cast<const f32x4*>(pp + 4);
-    }
-    hi[i] = ld_global_16(h_in + off);
-    if constexpr (BL) { bv[i] = ld_global_16(bias + c); lv[i] = ld_global_16(ls + c); }
-    if constexpr (NORM != 0) wv[i] = ld_global_16(nw + c);
-    if constexpr (NORM == 2) nbv[i] = ld_global_16(nb + c);
-  }
-  u32x4 hv[NCH];
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int u = 0; u < SX; ++u)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { v[j] += q[i][2 * u][j]; v[4 + j] += q[i][2 * u + 1][j]; }
-    u32x4 hr;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float lo = v[2 * j], hi2 = v[2 * j + 1];
-      if constexpr (BL) {
-        lo = (lo + bf16lo_to_f32(bv[i][j])) * bf16lo_to_f32(lv[i][j]);
-        hi2 = (hi2 + bf16hi_to_f32(bv[i][j])) * bf16hi_to_f32(lv[i][j]);
-      }
-      hr[j] = pack_bf16x2(bf16lo_to_f32(hi[i][j]) + lo, bf16hi_to_f32(hi[i][j]) + hi2);
-      const float a0 = bf16lo_to_f32(hr[j]), a1 = bf16hi_to_f32(hr[j]);
-      s1 += a0 + a1;
-      s2 += a0 * a0 + a1 * a1;
-    }
-    hv[i] = hr;
-    st_global_16(h_out + (size_t)row * C + (lane + 64 * i) * 8, hr);
-  }
-  if constexpr (NORM == 0) return;
-  s1 = wave_sum(s1);
-  float mean = 0.f, rs;
-  if constexpr (NORM == 1) {
-    rs = rsqrtf(wave_sum(s2) / (float)C + eps);
+#define VL_WG_X blockIdx.x
+#define VL_WG_Y blockIdx.y
+#define VL_WG_Z blockIdx.z
+#define VL_GRID_X gridDim.x
+#define VL_GRID_Y gridDim.y
+#include "reduce_norm_exact.inc"
+#undef VL_WG_X
+#undef VL_WG_Y
+#undef VL_WG_Z
+#undef VL_GRID_X
+#undef VL_GRID_Y
+}
+
+// Co-hosted seam (csrc/chain_kernels.h): the seam's rows HR to a workgroup of the GUEST's block size (a row is wave-local: packing changes no bits; the other waves
+// of a host workgroup return at once), the guest's workgroups behind them.  Neither side asks for much LDS, so host and guest workgroups share CUs -- the seam is a
+// latency-bound one-wave-per-row launch that leaves nearly every CU's memory pipeline idle.
+struct ReduceNormP {
+  const bf16_t* h_in; const float* partials; const bf16_t* nw; float eps; bf16_t* h_out; bf16_t* x_out; int M;
+};
+template <class G, int NORM, int NCH, int SX, int HR>
+__global__ __launch_bounds__(G::THREADS) void reduce_norm_exact_cohost_kernel(ReduceNormP h, typename G::P gp, int host_grid) {
+  static_assert(HR * 64 <= G::THREADS, "host rows per workgroup: one wave each");
+  if ((int)blockIdx.x < host_grid) {
+    const int wave = threadIdx.x >> 6, row = (int)blockIdx.x * HR + wave;
+    if (wave >= HR || row >= h.M) return;
+    reduce_norm_exact_body<NORM, NCH, SX, false>(h.h_in, h.partials, nullptr, nullptr, h.nw, nullptr, h.eps, h.h_out, h.x_out, h.M, row);
   } else {
-    mean = s1 / (float)C;
-    float vs = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float a0 = bf16lo_to_f32(hv[i][j]) - mean, a1 = bf16hi_to_f32(hv[i][j]) - mean;
-        vs += a0 * a0 + a1 * a1;
-      }
-    rs = rsqrtf(wave_sum(vs) / (float)C + eps);
+    G::run(gp, (int)blockIdx.x - host_grid);
   }
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    u32x4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float lo, hi2;
-      if constexpr (NORM == 1) {
-        lo = round_bf16(bf16lo_to_f32(hv[i][j]) * rs) * bf16lo_to_f32(wv[i][j]);
-        hi2 = round_bf16(bf16hi_to_f32(hv[i][j]) * rs) * bf16hi_to_f32(wv[i][j]);
-      } else {
-        lo = (bf16lo_to_f32(hv[i][j]) - mean) * rs * bf16lo_to_f32(wv[i][j]) + bf16lo_to_f32(nbv[i][j]);
-        hi2 = (bf16hi_to_f32(hv[i][j]) - mean) * rs * bf16hi_to_f32(wv[i][j]) + bf16hi_to_f32(nbv[i][j]);
-      }
-      o[j] = pack_bf16x2(lo, hi2);
-    }
-    st_global_16(x_out + (size_t)row * C + (lane + 64 * i) * 8, o);
-  }
+}
+template <class G, int SX>
+static int launch_reduce_norm_cohost(const ReduceNormP& h, const typename G::P& gp, int guest_wgs, int guest_lds, hipStream_t st) {
+  constexpr int HR = 2;
+  constexpr auto kernel = reduce_norm_exact_cohost_kernel<G, 1, 3, SX, HR>;
+  const int host_grid = (h.M + HR - 1) / HR;
+  if (guest_lds > 0) { if (int rc = set_max_lds_once(kernel, guest_lds)) return rc; }
+  if (vl_cohost_lab_zero_guests()) guest_wgs = 0;
+  hipLaunchKernelGGL(kernel, dim3(host_grid + guest_wgs), dim3(G::THREADS), guest_lds, st, h, gp, host_grid);
+  VL_LAUNCH_CHECK();
+  vl_cohost_count_fused();
+  return 0;
 }
 
 template <int NORM, int NCH, bool BL>
@@ -1397,4 +1377,23 @@ extern "C" int vlaser_reduce_norm(const void* h_in, const float* partials, int S
 #undef RN_ARGS
   VL_LAUNCH_CHECK();
   return 0;
+}
+
+/* vlaser_reduce_norm + a guest launch (include/vlaser_hip.h, co-hosted launches).  Fused: the joint prefill's two seams (C = 1536, RMSNorm, no bias; 3 slabs with the
+   expert's o_proj, 7 slabs with its down projection); host then guest otherwise. */
+extern "C" int vlaser_reduce_norm_cohost(const void* h_in, const float* partials, int S, const void* bias, const void* ls, int norm_kind, const void* nw, const void* nb,
+                                         float eps, void* h_out, void* x_out, int M, int C, const VlaserCohostGuest* guest, vl_stream_t s) {
+  if (guest && h_in && partials && h_out && nw && x_out && !bias && !ls && norm_kind == 1 && C == 1536 && M > 0 && (S == 3 || S == 7)) {
+    const ReduceNormP h = {(const bf16_t*)h_in, partials, (const bf16_t*)nw, eps, (bf16_t*)h_out, (bf16_t*)x_out, M};
+    int wgs, lds;
+    if (S == 3) {
+      ChainOprojP gp;
+      if (vl_cohost_chain_oproj(guest, &gp, &wgs, &lds)) return launch_reduce_norm_cohost<GuestChainOproj, 3>(h, gp, wgs, lds, (hipStream_t)s);
+    } else {
+      ChainDownP gp;
+      if (vl_cohost_chain_down(guest, &gp, &wgs)) return launch_reduce_norm_cohost<GuestChainDown, 7>(h, gp, wgs, 0, (hipStream_t)s);
+    }
+  }
+  if (int rc = vlaser_reduce_norm(h_in, partials, S, bias, ls, norm_kind, nw, nb, eps, h_out, x_out, M, C, s)) return rc;
+  return vl_cohost_guest_launch(guest, s);
 }

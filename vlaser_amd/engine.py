@@ -276,6 +276,11 @@ class VitEngine:
         return self.feat[:n_tok]
 
 
+def seam_is_split(sp, M):
+    """Whether residual_seam takes its split-K GEMM + fused reduce / residual / norm composition (two launches) for `sp` slabs of M rows."""
+    return sp >= 3 or (sp == 2 and M < 2048)
+
+
 def residual_seam(a, w, h, part, M, N, K, x_out=None, bias=None, ls=None, norm=0, norm_w=None, norm_b=None, eps=1e-6, splits=None):
     """The seam behind an N = hidden GEMM: h += [ls *] (a @ w^T [+ bias]); x_out = norm(h) (norm: 0 none / 1 RMS / 2 LayerNorm).  Two compositions of the same arithmetic
     and the same rounding points (h rounded to bf16 once, the norm taken of the rounded h):
@@ -286,7 +291,7 @@ def residual_seam(a, w, h, part, M, N, K, x_out=None, bias=None, ls=None, norm=0
         the fp32 summation order.  (The one-tile ViT proj, 2 slabs of 1025 rows, is 3 us faster as a pair in isolation and EQUAL inside the chunk -- same-box A/B 11.775 vs
         11.778 ms -- so the small shapes keep the slab path and their bit-exact history.)"""
     sp = ops.gemm_splits(M, N, K, part.numel()) if splits is None else splits
-    if sp >= 3 or (sp == 2 and M < 2048):
+    if seam_is_split(sp, M):
         ops.gemm(L.EPI_PARTIAL, a, w, out_f32=part, k_splits=sp)
         ops.reduce_norm(h, part, sp, M, N, h, x_out, bias=bias, ls=ls, norm=norm if x_out is not None else 0, norm_w=norm_w, norm_b=norm_b, eps=eps)
         return
@@ -321,6 +326,48 @@ def prefill_begin(stack: QwenStack, buf: PrefillBuffers, h, M):
     ops.rmsnorm(h, stack.layers[0].ln_in, stack.llm.rms_norm_eps, out=buf.x[:M])
 
 
+def prefill_layer_launches(stack: QwenStack, lw: QwenLayerWeights, buf: PrefillBuffers, h, cache: KVCache, layer, rope, pos_ids, batch,
+                           tok_per_batch, attn_mode, valid_len=None, blk_start=0, causal_off=0, kv_len=None, skip_post_attn=False,
+                           next_norm_w=None, slot_base=0, dense_mask=None):
+    """prefill_layer as its launches in order: [(name, fn)], run as fn() -- or fn(guest=...) for a co-hosted launch (ops.cohost_guest; PiZero._run_joint).  Names: 'qkv',
+    'attn', then per split-K seam its GEMM and its reduce + residual + norm launch: 'o', 'seam_o', 'gu', 'down', 'seam_d'.  A seam that residual_seam composes
+    the other way (whole-K GEMM with the residual in its epilogue + a norm launch) is ONE entry, 'o' / 'down', that takes no guest."""
+    llm = stack.llm
+    M = batch * tok_per_batch
+    nq, nkv, hd = stack.nq, stack.nkv, llm.head_dim
+    H, I = llm.hidden_size, llm.intermediate_size
+    x, q, ao, act = buf.x[:M], buf.q[:M], buf.ao[:M], buf.act[:M]
+    out = [('qkv', lambda guest=None: ops.gemm(L.EPI_QKV_ROPE, x, lw.wqkv, bias=lw.bqkv, q_out=q, k_cache=cache.k[layer], vt_cache=cache.vt[layer], rope_cos=rope[0],
+                                              rope_sin=rope[1], pos_ids=pos_ids, n_q_heads=nq, n_kv_heads=nkv, s_max=cache.s_max, tok_per_batch=tok_per_batch,
+                                              slot_base=slot_base, guest=guest))]
+    if skip_post_attn:          # the last layer of a mixture whose hidden states nobody reads (the VLM / proprio rows of the VLA): only its K / V are needed
+        return out
+    ks, vs = cache.strides()
+    out.append(('attn', lambda guest=None: ops.attn_prefill(
+        q, cache.k[layer], cache.vt[layer], ao, batch, tok_per_batch, tok_per_batch if kv_len is None else kv_len, nq, nkv, hd,
+        (tok_per_batch * nq * hd, hd, nq * hd), ks, vs, (tok_per_batch * nq * hd, nq * hd), cache.s_max, hd ** -0.5,
+        L.ATTN_DENSE if dense_mask is not None else attn_mode, causal_off=causal_off, valid_len=valid_len, blk_start=blk_start, q_row_off=slot_base,
+        dense_mask=dense_mask, guest=guest)))        # dense_mask: fp32 view [B, tok_per_batch, >= kv_len] of the reference's additive mask (general masks, ABI 8)
+    part = buf.part
+    eps = llm.rms_norm_eps
+
+    def seam(name, a, w, K, x_out, norm_w):
+        sp = ops.gemm_splits(M, H, K, part.numel())
+        norm = 1 if x_out is not None else 0
+        if not seam_is_split(sp, M):
+            def whole(guest=None):
+                assert guest is None, 'a whole-K seam hosts no guest'
+                residual_seam(a, w, h, part, M, H, K, x_out, norm=norm, norm_w=norm_w, eps=eps, splits=sp)
+            return [(name, whole)]
+        return [(name, lambda guest=None: ops.gemm(L.EPI_PARTIAL, a, w, out_f32=part, k_splits=sp, guest=guest)),
+                ('seam_' + name[0], lambda guest=None: ops.reduce_norm(h, part, sp, M, H, h, x_out, norm=norm, norm_w=norm_w, eps=eps, guest=guest))]
+
+    out += seam('o', ao, lw.wo, nq * hd, x, lw.ln_post)
+    out.append(('gu', lambda guest=None: ops.gemm(L.EPI_SWIGLU, x, lw.wgu, out=act, guest=guest)))
+    out += seam('down', act, lw.wdown, I, x if next_norm_w is not None else None, next_norm_w)
+    return out
+
+
 def prefill_layer(stack: QwenStack, lw: QwenLayerWeights, buf: PrefillBuffers, h, cache: KVCache, layer, rope, pos_ids, batch,
                   tok_per_batch, attn_mode, valid_len=None, blk_start=0, causal_off=0, kv_len=None, skip_post_attn=False,
                   next_norm_w=None, slot_base=0, dense_mask=None):
@@ -330,26 +377,9 @@ def prefill_layer(stack: QwenStack, lw: QwenLayerWeights, buf: PrefillBuffers, h
     next_norm_w is given (next layer's input_layernorm or the final norm).  h is updated in place.
     o_proj / down_proj run split-K (their [M, H] outputs have too few tiles to fill 256 CUs); the fp32 slabs are
     reduced by ONE fused kernel that also adds the residual and applies the following RMSNorm."""
-    llm = stack.llm
-    M = batch * tok_per_batch
-    nq, nkv, hd = stack.nq, stack.nkv, llm.head_dim
-    H, I = llm.hidden_size, llm.intermediate_size
-    x, q, ao, act = buf.x[:M], buf.q[:M], buf.ao[:M], buf.act[:M]
-    ops.gemm(L.EPI_QKV_ROPE, x, lw.wqkv, bias=lw.bqkv, q_out=q, k_cache=cache.k[layer], vt_cache=cache.vt[layer], rope_cos=rope[0],
-             rope_sin=rope[1], pos_ids=pos_ids, n_q_heads=nq, n_kv_heads=nkv, s_max=cache.s_max, tok_per_batch=tok_per_batch, slot_base=slot_base)
-    if skip_post_attn:          # the last layer of a mixture whose hidden states nobody reads (the VLM / proprio rows of the VLA): only its K / V are needed
-        return
-    ks, vs = cache.strides()
-    ops.attn_prefill(q, cache.k[layer], cache.vt[layer], ao, batch, tok_per_batch, tok_per_batch if kv_len is None else kv_len, nq, nkv, hd,
-                     (tok_per_batch * nq * hd, hd, nq * hd), ks, vs, (tok_per_batch * nq * hd, nq * hd), cache.s_max, hd ** -0.5,
-                     L.ATTN_DENSE if dense_mask is not None else attn_mode, causal_off=causal_off, valid_len=valid_len, blk_start=blk_start, q_row_off=slot_base,
-                     dense_mask=dense_mask)        # dense_mask: fp32 view [B, tok_per_batch, >= kv_len] of the reference's additive mask (general masks, ABI 8)
-    part = buf.part
-    sp_o, sp_d = ops.gemm_splits(M, H, nq * hd, part.numel()), ops.gemm_splits(M, H, I, part.numel())
-    residual_seam(ao, lw.wo, h, part, M, H, nq * hd, x, norm=1, norm_w=lw.ln_post, eps=llm.rms_norm_eps, splits=sp_o)
-    ops.gemm(L.EPI_SWIGLU, x, lw.wgu, out=act)
-    residual_seam(act, lw.wdown, h, part, M, H, I, x if next_norm_w is not None else None, norm=1 if next_norm_w is not None else 0, norm_w=next_norm_w,
-                  eps=llm.rms_norm_eps, splits=sp_d)
+    for _, fn in prefill_layer_launches(stack, lw, buf, h, cache, layer, rope, pos_ids, batch, tok_per_batch, attn_mode, valid_len, blk_start, causal_off, kv_len,
+                                        skip_post_attn, next_norm_w, slot_base, dense_mask):
+        fn()
 
 
 class SkinnyBuffers:
@@ -378,6 +408,19 @@ def skinny_layer(stack: QwenStack, lw: QwenLayerWeights, sb: SkinnyBuffers, h_in
     (h, partials, n_partials) describing this layer's output residual the same way.
     The kernel path (layer_path), the argument structs and the launch list of a (layer, input buffers, geometry) are built once and re-launched: only the cache slot,
     the key count and its split factor change from step to step (greedy decode is otherwise host-bound on deciding and struct building)."""
+    plan = skinny_layer_plan(stack, lw, sb, h_in, partials, n_partials, cache, layer, rope, pos_ids, batch, tok_per_batch, slot_base, kv_len, attn_mode, valid_len,
+                             blk_start, skip_post_attn, first_tok_kv_len, dense_mask)
+    stream = torch.cuda.current_stream().cuda_stream
+    for name, launch, args in plan.launches:
+        if name not in skip:                  # `skip` (bench.py only): in-chain timing of one launch = chain with it - chain without it
+            launch(*args, stream)
+    return plan.result
+
+
+def skinny_layer_plan(stack, lw, sb, h_in, partials, n_partials, cache, layer, rope, pos_ids, batch, tok_per_batch, slot_base, kv_len, attn_mode, valid_len=None,
+                      blk_start=0, skip_post_attn=False, first_tok_kv_len=0, dense_mask=None):
+    """The plan of a skinny_layer call, brought up to date for this call (cache slot, key count, split factor), without launching anything: .launches in order,
+    .result = what the layer hands on."""
     M = batch * tok_per_batch
     # the key holds what the plan depends on; of kv_len, the path only reads whether the chain attention + o_proj pair is built for its split count (1..16)
     key = (layer, M, tok_per_batch, attn_mode, h_in.data_ptr(), 0 if partials is None else partials.data_ptr(), n_partials,
@@ -396,11 +439,27 @@ def skinny_layer(stack: QwenStack, lw: QwenLayerWeights, sb: SkinnyBuffers, h_in
     a.kv_len, a.n_splits, a.blk_start = kv_len, nsp, blk_start
     if not skip_post_attn:
         plan.o[0].attn_splits = nsp          # (the key count, hence the split count, moves from step to step in an eager decode)
-    stream = torch.cuda.current_stream().cuda_stream
-    for name, launch, args in plan.launches:
-        if name not in skip:                  # `skip` (bench.py only): in-chain timing of one launch = chain with it - chain without it
-            launch(*args, stream)
-    return plan.result
+    return plan
+
+
+_GUEST_KINDS = {'qkv': L.GUEST_CHAIN_QKV, 'attn': L.GUEST_CHAIN_ATTN, 'o': L.GUEST_CHAIN_OPROJ, 'gu': L.GUEST_CHAIN_GU, 'down': L.GUEST_CHAIN_DOWN}
+
+
+def plan_guest(plan, name):
+    """Launch `name` of a chain plan (chain and chain_ao, bf16 weights) as the guest descriptor of a co-hosted launch; built once per plan.  It points at the plan's own
+    argument struct, so what skinny_layer_plan brings up to date is what the host's launch reads."""
+    g = plan.guests.get(name)
+    if g is None:
+        assert plan.chain and plan.chain_ao
+        launch, args = next((l, a) for n, l, a in plan.launches if n == name)
+        if name == 'down':
+            assert launch is _chain_down
+            sb, W4, M, H, I, _ = args
+            a = ops.chain_down_args(sb.act, W4, sb.hB, sb.hC, M, H, I)
+        else:
+            a = args[0]
+        g = plan.guests[name] = ops.cohost_guest(_GUEST_KINDS[name], a)
+    return g
 
 
 def _chain_down_w8(sb, lw, M, H, I, down, stream):
@@ -426,7 +485,7 @@ def _build_plan(stack, lw, sb, h_in, partials, n_partials, cache, layer, rope, p
     if dense_mask is not None:
         attn_mode = L.ATTN_DENSE
     ks, vs = cache.strides()
-    plan = SimpleNamespace(chain=chain, chain_ao=chain_ao)
+    plan = SimpleNamespace(chain=chain, chain_ao=chain_ao, guests={})
     plan.qkv = ops.skinny_args(h_in, lw.sk_qkv, M, partials=partials, n_partials=n_partials, norm_w=lw.ln_in, eps=llm.rms_norm_eps,
                                h_out=sb.hA, bias=lw.bqkv_sk, q_out=sb.q, k_cache=cache.k[layer], vt_cache=cache.vt[layer], rope_cos=rope[0],
                                rope_sin=rope[1], pos_ids=pos_ids, n_q_heads=nq, n_kv_heads=nkv, s_max=cache.s_max,

@@ -1,5 +1,6 @@
 """Thin torch-tensor wrappers over the C ABI (include/vlaser_hip.h).  PyTorch is plumbing here: it owns device
 memory and the stream; every op below is a launch of a hand-written gfx950 kernel in libvlaser_hip.so."""
+import ctypes
 import ctypes as C
 import math
 
@@ -119,10 +120,31 @@ def gemm(epi, A, W, out=None, bias=None, res=None, ls=None, N=None, **kw):
     part = kw.get('out_f32')
     if epi == L.EPI_PARTIAL and isinstance(part, torch.Tensor) and part.numel() < kw.get('k_splits', 1) * M * a.N:
         raise ValueError(f'vlaser_gemm: {kw.get("k_splits", 1)} fp32 slabs of [{M},{a.N}] do not fit the {part.numel()}-element partial buffer')
+    guest = kw.pop('guest', None)          # a co-hosted launch (cohost_guest): this GEMM's grid carries the guest's workgroups where a fused instantiation exists
     for k, v in kw.items():
         setattr(a, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
-    L.check(L.lib().vlaser_gemm(epi, C.byref(a), _stream()), 'vlaser_gemm')
+    if guest is not None:
+        L.check(L.lib().vlaser_gemm_cohost(epi, C.byref(a), C.byref(guest), _stream()), 'vlaser_gemm_cohost')
+    else:
+        L.check(L.lib().vlaser_gemm(epi, C.byref(a), _stream()), 'vlaser_gemm')
     return out
+
+
+def cohost_guest(kind, args):
+    """Guest descriptor of a co-hosted launch: kind = L.GUEST_*, args = the guest's own ctypes argument struct (SkinnyArgs / AttnArgs / ChainDownArgs), read when the
+    host is launched.  The descriptor keeps the struct alive."""
+    g = L.CohostGuest()
+    g.kind, g.args = kind, C.addressof(args)
+    g._args = args
+    return g
+
+
+def chain_down_args(x, W4, res, h_out, M, N, K):
+    """vlaser_chain_down's arguments as a struct (the guest of a co-hosted seam)."""
+    assert x.dtype == BF16 and res.dtype == BF16 and h_out.dtype == BF16 and x.stride(-1) == 1 and res.data_ptr() != h_out.data_ptr()
+    a = L.ChainDownArgs()
+    a.x, a.ldx, a.W, a.res, a.h_out, a.M, a.N, a.K = x.data_ptr(), x.stride(0), W4.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K
+    return a
 
 
 def gemm_nn(epi, A, B, out=None, **kw):
@@ -206,9 +228,12 @@ def _attn_args(q, k, vt, out, batch, sq, kv_len, n_q, n_kv, hd, q_str, k_str, vt
     return a
 
 
-def attn_prefill(*args, **kw):
+def attn_prefill(*args, guest=None, **kw):
     a = _attn_args(*args, **kw)
-    L.check(L.lib().vlaser_attn_prefill(C.byref(a), _stream()), 'vlaser_attn_prefill')
+    if guest is not None:
+        L.check(L.lib().vlaser_attn_prefill_cohost(C.byref(a), C.byref(guest), _stream()), 'vlaser_attn_prefill_cohost')
+    else:
+        L.check(L.lib().vlaser_attn_prefill(C.byref(a), _stream()), 'vlaser_attn_prefill')
 
 
 def attn_bwd(q, k, vt, o, d_o, lse, delta_ws, dq, dk, dv, S, n_q, n_kv, s_max, scale, causal=True, kv_valid=None, head_dim=128):
@@ -759,8 +784,12 @@ def fold_action_encoder(w1, b1, w2, b2, W, adim, n_steps, max_period):
     return w21, cs
 
 
-def reduce_norm(h_in, partials, n_partials, M, C, h_out, x_out=None, bias=None, ls=None, norm=0, norm_w=None, norm_b=None, eps=1e-6):
-    """h_out = h_in + [ls*](sum partials [+bias]); x_out = norm(h_out) (norm: 0 none, 1 RMS, 2 LayerNorm)."""
+def reduce_norm(h_in, partials, n_partials, M, C, h_out, x_out=None, bias=None, ls=None, norm=0, norm_w=None, norm_b=None, eps=1e-6, guest=None):
+    """h_out = h_in + [ls*](sum partials [+bias]); x_out = norm(h_out) (norm: 0 none, 1 RMS, 2 LayerNorm).  guest: a co-hosted launch (cohost_guest)."""
+    if guest is not None:          # (the width argument shadows the module's ctypes alias here)
+        L.check(L.lib().vlaser_reduce_norm_cohost(_p(h_in), _p(partials), n_partials, _p(bias), _p(ls), norm, _p(norm_w), _p(norm_b), eps,
+                                                  h_out.data_ptr(), _p(x_out), M, C, ctypes.byref(guest), _stream()), 'vlaser_reduce_norm_cohost')
+        return
     L.check(L.lib().vlaser_reduce_norm(_p(h_in), _p(partials), n_partials, _p(bias), _p(ls), norm, _p(norm_w), _p(norm_b), eps,
                                        h_out.data_ptr(), _p(x_out), M, C, _stream()), 'vlaser_reduce_norm')
 

@@ -22,7 +22,8 @@ import torch
 from . import _lib as L
 from . import ops, prep
 from .config import VLAConfig
-from .engine import BF, KVCache, PrefillBuffers, QwenStack, SkinnyBuffers, VitEngine, prefill_begin, prefill_layer, skinny_layer
+from .engine import (BF, KVCache, PrefillBuffers, QwenStack, SkinnyBuffers, VitEngine, plan_guest, prefill_begin, prefill_layer, prefill_layer_launches, skinny_layer,
+                     skinny_layer_plan)
 
 
 def canonicalize_vla_state_dict(sd):
@@ -108,6 +109,44 @@ def stage_pixels(pixel_values, out, dev):
     return out
 
 
+# Co-hosted joint prefill ('cohost'): which prefill launch of VLM layer l carries which launch of expert layer l of Euler step 0 (guest -> host, names of
+# engine.prefill_layer_launches / of a chain plan's launches).  The q/k/v GEMM hosts nobody: it writes the prefix K / V^T its own layer's guests read.
+COHOST_PAIRS = {'qkv': 'attn', 'attn': 'o', 'o': 'seam_o', 'gu': 'gu', 'down': 'seam_d'}
+
+
+def cohost_plan(hosts, guests, enabled=tuple(COHOST_PAIRS)):
+    """The launch order of the co-hosted joint prefill, from the two launch lists alone (no tensors): hosts = [(layer, name)] of the prefill in launch order, guests =
+    [(layer, name)] of the expert's first pass in launch order, enabled = the guest names whose pair is switched on.  Returns [(host | None, guest | None)] in issue
+    order: (host, guest) = one co-hosted launch, (host, None) = the host alone, (None, guest) = the guest as a launch of its own.
+    A guest rides in the launch COHOST_PAIRS names, of its own layer.  A guest whose pair is off, or whose layer has no such launch (the last VLM layer stops after its
+    q/k/v GEMM), is launched on its own directly behind that host -- behind its layer's q/k/v GEMM where the host does not exist -- and never in front of an earlier
+    guest: the expert's launches keep their order, every one of them is issued exactly once, and none before the q/k/v GEMM that writes the prefix keys it reads."""
+    hosts, guests = list(hosts), list(guests)
+    where = {h: i for i, h in enumerate(hosts)}
+    out, gi = [], 0
+    for hi, host in enumerate(hosts):
+        paired = None
+        if gi < len(guests):
+            gl, gn = guests[gi]
+            if gn in enabled and (gl, COHOST_PAIRS.get(gn)) == host:
+                paired = guests[gi]
+                gi += 1
+        out.append((host, paired))
+        while gi < len(guests):          # guests that no later launch will carry and whose inputs are complete
+            gl, gn = guests[gi]
+            at = where.get((gl, COHOST_PAIRS.get(gn)))      # (a launch name without a pair -- a stack off the chain path -- has no host)
+            if at is None:
+                at = where.get((gl, 'qkv'), -1)
+            elif gn in enabled and at > hi:
+                break                    # its host is still to come
+            if at > hi:
+                break
+            out.append((None, guests[gi]))
+            gi += 1
+    out += [(None, g) for g in guests[gi:]]
+    return out
+
+
 class _ActionChunk(torch.Tensor):
     """The tensor `infer_action` returns when it was handed the reference's dense masks: an ordinary device tensor that remembers the model whose deferred mask
     check covers it.  The check itself never synchronises (pizero.py::_poll_errors); but the first thing a caller does with a chunk is bring it to the host
@@ -152,7 +191,14 @@ class PiZero:
     #          footprint (1.16 -> 0.58 GB at full depth).  Weight-only: bf16 MFMAs and summation orders unchanged, so the chunk is bit-identical to the default path run
     #          on the dequantised weights.  It is NOT the bf16 model: on the synthetic test model the chunk moves by 1.5e-2 (the reference's own bf16 mode sits 6.5e-3 to
     #          1.6e-2 from its fp32 chunk); the deviation on released checkpoints is unmeasured.  A/B: profiles/fp8_mlp_ab.md.  OFF by default
-    EULER_DEFAULT = 'qkv16,gu16,glue1,chain'      # (gu16 ON with chain since r05: 224 workgroups x 5 units instead of 187 x 3, 11.79 -> 11.68 ms per chunk, same-box A/B)
+    #   cohost (needs chain + qkv16 + gu16 + glue1; batch 1 with the proprio row riding, bf16 expert weights, no general masks -- today's schedule otherwise): the first
+    #          pass through the expert (Euler step 0, the five rows that carry the proprio token) is issued INSIDE the joint prefill: expert layer l needs the prefix K / V^T
+    #          of VLM layer l and its own previous layer only, so its launches ride as extra workgroups of the prefill's own launches (COHOST_PAIRS; csrc/chain_kernels.h)
+    #          on the CUs their single-round grids leave idle.  One queue, no flags, no polling; bit-identical (same bodies, same summation orders).
+    #          'cohost' = every pair; 'cohost=qkv+gu' = only those pairs ride, the other guests run as launches of their own behind their hosts.  profiles/cohost_ab.md
+    #          ON for the four pairs that pass the per-pair A/B (tools/micro/cohost_ab.py, one model instance): qkv, attn, o, gu; hosting the down projection in the second seam
+    #          is worth 0.04-0.05 ms, less than the 0.06 ms run-to-run spread of that job, and stays opt-in ('cohost' = all five)
+    EULER_DEFAULT = 'qkv16,gu16,glue1,chain,cohost=qkv+attn+o+gu'      # (gu16 ON with chain since r05: 224 workgroups x 5 units instead of 187 x 3, 11.79 -> 11.68 ms per chunk, same-box A/B)
 
     ERR_BITS = {1: 'image_text_proprio_mask: the keys the proprio row sees are not a contiguous valid prefix',
                 2: 'image_text_proprio_mask: a valid-prefix row (or the proprio row\'s own key) does not have the prefix pattern of build_causal_mask_and_position_ids',
@@ -199,6 +245,16 @@ class PiZero:
             if missing:
                 raise ValueError(f"Euler option 'mlp8' (expert_mlp_weights='fp8') needs {', '.join(missing)}: the e4m3 MLP weights are read by the chain kernels' 16-row-unit forms only")
         self.expert_mlp_weights = 'fp8' if 'mlp8' in self.euler_opts else 'bf16'
+        # 'cohost' / 'cohost=a+b': the pairs of the co-hosted joint prefill that are switched on (None: the option is off)
+        self.cohost_pairs = None
+        for o in self.euler_opts:
+            if o == 'cohost' or o.startswith('cohost='):
+                pairs = tuple(COHOST_PAIRS) if o == 'cohost' else tuple(x for x in o[len('cohost='):].split('+') if x)
+                bad = [x for x in pairs if x not in COHOST_PAIRS]
+                missing = [x for x in ('chain', 'qkv16', 'gu16', 'glue1') if x not in self.euler_opts]
+                if bad or missing:
+                    raise ValueError(f"Euler option {o!r}: " + (f"unknown pair(s) {', '.join(bad)} (of {', '.join(COHOST_PAIRS)})" if bad else f"needs {', '.join(missing)}"))
+                self.cohost_pairs = pairs
         self._graphs = {}
         self._pos_state = None
         self._pos_next = None
@@ -339,8 +395,66 @@ class PiZero:
         """ViT + projector + scatter -> joint prefill -> Euler loop: three phases, separately callable so that bench.py can time each
         one from its own HIP graph (per-phase ms on the JSON line)."""
         self._run_vit(B)
-        self._run_prefill(B)
-        self._run_euler(B)
+        if self._cohost_ok(B):
+            fin = self._run_joint(B)
+            self._run_euler_glue1(B, first_pass=fin)
+        else:
+            self._run_prefill(B)
+            self._run_euler(B)
+
+    def _cohost_ok(self, B):
+        """Whether this call takes the co-hosted joint prefill: the option, and the one case its fused launches are built for."""
+        return (self.cohost_pairs is not None and self._glue1 and self._ride(B) and B == 1 and not self.general_masks and self.expert_mlp_weights == 'bf16')
+
+    def _run_joint(self, B):
+        """Joint prefill + the first pass through the expert (Euler step 0: proprio row + action rows) as ONE sequence of launches: expert layer l's five launches ride in
+        the launches of VLM layer l (cohost_plan).  Issues what _run_prefill and the first pass of _run_euler_glue1 issue -- the same kernels' bodies on the same arguments --
+        and returns the `fin` tuple that pass hands to the next vla_step.  Why a guest may share its host's launch (checked against the kernels):
+          (a) the host attention of layer l runs with kv_len = T and reads no cache slot >= T (K rows < T; V^T in 16-byte pieces of 8 keys below T, T a multiple of 64); its
+              guest, the expert's q/k/v, writes slots T .. T + 4 of the same layer.  The q/k/v GEMM that writes the slots < T of those V^T rows finished one launch earlier.
+          (b) the expert's attention of layer l (guest of the o_proj GEMM) reads the prefix K / V^T that the q/k/v GEMM of layer l wrote two launches earlier, and slots
+              T .. T + 4 that its own q/k/v wrote one launch earlier.
+          (c) host and guest of every pair write disjoint buffers: pbuf.*, h_vlm, pbuf.part and the cache slots < T against sb_pro.* and the slots >= T; valid_len is
+              read by both and written by neither.
+        The proprio encoder and the action encoder of step 0 depend on the call's inputs only and go first."""
+        cfg = self.cfg
+        llm, ex = cfg.base.llm, cfg.expert
+        T, na = self.max_image_text_tokens, self.num_action_tokens
+        nL = llm.num_hidden_layers
+        M, W, ad = B * na, cfg.action_hidden_size, cfg.action_dim
+        h_vlm = self.h_vlm[:B * T]
+        ops.small_linear(self.in_proprio, self.pe_w, self.pe_b, self.h5, B, W, cfg.proprio_dim)      # row 0
+        a0 = (self.action, self.action_b)[(self.num_inference_steps - 1) % 2]
+        assert a0 is self.noise_dst
+        ops.vla_step(a0, a0, self.ae_w21, self.ae_cs[0], self.ae_w3_raw, self.ae_b3, self.h5[1:1 + M], M, W, ad)
+        # the two launch lists
+        host_fn, hosts = {}, []
+        for i in range(nL):
+            last = i == nL - 1
+            for name, fn in prefill_layer_launches(self.vlm, self.vlm.layers[i], self.pbuf, h_vlm, self.cache, i, self.rope, self.pos_vlm, B, T, L.ATTN_PREFIX,
+                                                   valid_len=self.valid_len, blk_start=T, skip_post_attn=last, next_norm_w=None if last else self.vlm.layers[i + 1].ln_in):
+                host_fn[(i, name)] = fn
+                hosts.append((i, name))
+        plans, guests = [], []
+        h, parts, npart = self.h5, None, 0
+        for i in range(nL):
+            plan = skinny_layer_plan(self.expert, self.expert.layers[i], self.sb_pro, h, parts, npart, self.cache, i, self.rope, self.pos5, B, na + 1, T, T + 1 + na,
+                                     L.ATTN_PREFIX, valid_len=self.valid_len, blk_start=T, first_tok_kv_len=T + 1)
+            plans.append(plan)
+            guests += [(i, name) for name, _, _ in plan.launches]
+            h, parts, npart = plan.result
+        hostable = all(p.chain and p.chain_ao for p in plans)      # (a stack off the chain path has other launches: they all run on their own, in order)
+        stream = torch.cuda.current_stream().cuda_stream
+        prefill_begin(self.vlm, self.pbuf, h_vlm, B * T)
+        for host, guest in cohost_plan(hosts, guests, self.cohost_pairs if hostable else ()):
+            if host is None:
+                _, launch, args = next(l for l in plans[guest[0]].launches if l[0] == guest[1])
+                launch(*args, stream)
+            elif guest is None:
+                host_fn[host]()
+            else:
+                host_fn[host](guest=plan_guest(plans[guest[0]], guest[1]))
+        return (h, parts, npart, M + 1, 1, self.expert.norm, ex.rms_norm_eps, self.ad_w, self.ad_b)       # row 0 = the proprio row: skipped
 
     def _run_vit(self, B):
         # a1-a7, a12: ViT tiles -> projector -> scatter into the (zero-padded) text embeddings
@@ -427,11 +541,12 @@ class PiZero:
             ops.vla_euler(h, parts, npart, M, self.expert.norm, ex.rms_norm_eps, self.ad_w, self.ad_b, self.action, W, cfg.action_dim, dt,
                           clip if clip is not None else 0.0, clip is not None and s == n - 1, vel_out=self.vel_trace[s], ring=ring[0], ring_ctr=ring[1], method=cfg.integration_method)
 
-    def _run_euler_glue1(self, B, skip=()):
+    def _run_euler_glue1(self, B, skip=(), first_pass=None):
         """The same integration with ONE launch between two passes through the expert's layers (`vlaser_vla_step`: tail of step s-1 + action
         encoder of step s) instead of four (vla_euler, vla_prep, linear_2 + swish, linear_3): 30 launches of ~5 us less per chunk.  linear_1 and the
         time embedding are folded into linear_2 at load time, so the encoder output differs from the 4-launch path in the last bf16 bit of a few
-        elements (no longer bit-identical to `VLASER_EULER=qkv16`; same tolerance against the oracle and the reference goldens)."""
+        elements (no longer bit-identical to `VLASER_EULER=qkv16`; same tolerance against the oracle and the reference goldens).
+        first_pass: the `fin` of Euler step 0 when _run_joint has already issued that step's encoder launch and its pass through the layers."""
         cfg = self.cfg
         llm, ex = cfg.base.llm, cfg.expert
         T, na = self.max_image_text_tokens, self.num_action_tokens
@@ -446,6 +561,9 @@ class PiZero:
         fin = None
         for s in range(n):
             first = ride and s == 0
+            if first and first_pass is not None:
+                fin = first_pass
+                continue
             h_enc = self.h5[1:1 + M] if first else self.h_act
             if fin is None:
                 ops.vla_step(acts[p], acts[p], self.ae_w21, self.ae_cs[s], self.ae_w3_raw, self.ae_b3, h_enc, M, W, ad)
