@@ -284,7 +284,8 @@ int vlaser_chain_down_w8(const void* x, int ldx, const void* W, const float* w_s
  * the host, or the guest's shape, has no fused instantiation it launches the host, then the guest, and returns success.  Fused instantiations (B = 1, T = 384, 5 expert rows):
  *   vlaser_attn_prefill_cohost : attn_prefill<128, 2, 64> + VL_GUEST_CHAIN_QKV        vlaser_gemm_cohost : 64x128 PARTIAL (o_proj) + VL_GUEST_CHAIN_ATTN,
  *   vlaser_reduce_norm_cohost  : C = 1536 RMS, 3 slabs + VL_GUEST_CHAIN_OPROJ,                               128x256 SWIGLU (gate/up) + VL_GUEST_CHAIN_GU
- *                                C = 1536 RMS, 7 slabs + VL_GUEST_CHAIN_DOWN
+ *                                C = 1536 RMS, 7 slabs + VL_GUEST_CHAIN_DOWN                          64x64 QKV_ROPE (q/k/v, 192 tiles) + VL_GUEST_CHAIN_DOWN
+ * (the q/k/v GEMM runs its guest in the looped form, four of vlaser_chain_down's workgroups to one: its 64 idle CUs take one workgroup each.)
  * guest == NULL or kind VL_GUEST_NONE: the host alone. */
 enum { VL_GUEST_NONE = 0, VL_GUEST_CHAIN_QKV = 1, VL_GUEST_CHAIN_ATTN = 2, VL_GUEST_CHAIN_OPROJ = 3, VL_GUEST_CHAIN_GU = 4, VL_GUEST_CHAIN_DOWN = 5 };
 typedef struct VlaserCohostGuest {
@@ -296,6 +297,7 @@ typedef struct VlaserChainDownArgs {      /* vlaser_chain_down's arguments */
 } VlaserChainDownArgs;
 int vlaser_cohost_fused_count(void);            /* launches so far that carried their guest in their own grid (the fallback returns the same 0: this tells them apart) */
 int vlaser_cohost_lab(int mode);                /* timing tools only: 1 = fused kernels run with zero guest workgroups and the guest is skipped (host-alone check); returns the previous mode */
+int vlaser_chain_down_looped(const void* x, int ldx, const void* W, const void* res, void* h_out, int M, int N, int K, vl_stream_t stream);      /* the looped form on its own (tests, tools): vlaser_chain_down's bits */
 int vlaser_gemm_cohost(int epi, const VlaserGemmArgs* args, const VlaserCohostGuest* guest, vl_stream_t stream);
 int vlaser_attn_prefill_cohost(const VlaserAttnArgs* args, const VlaserCohostGuest* guest, vl_stream_t stream);
 int vlaser_reduce_norm_cohost(const void* h_in, const float* partials, int n_partials, const void* bias, const void* ls, int norm_kind, const void* norm_w, const void* norm_b,

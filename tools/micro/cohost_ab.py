@@ -4,6 +4,9 @@ variants in turn.
 
     python tools/micro/cohost_ab.py                      # off, all five, each pair alone, each pair left out
     python tools/micro/cohost_ab.py off qkv+attn all     # named sets
+    python tools/micro/cohost_ab.py lag                  # the lagged pair: off, the four default pairs, those + down_next, down_next alone, all, off
+
+`down_next` in a set = the down projection rides in the next layer's q/k/v GEMM (pizero.COHOST_LAGGED); `all` = the five pairs of COHOST_PAIRS.
 
 Prints median / min ms per chunk and, against `off` and against `all`, the difference of the medians with the spread of `off` over its rounds."""
 import os
@@ -19,10 +22,15 @@ sys.path.insert(0, ROOT)
 def main():
     import bench
     from vlaser_amd import config as C, synth
-    from vlaser_amd.pizero import COHOST_PAIRS, PiZeroInference
+    from vlaser_amd.pizero import COHOST_PAIRS, LAG_TOKENS, PiZeroInference
     names = list(COHOST_PAIRS)
     variants = sys.argv[1:] or (['off', 'all'] + names + ['+'.join(x for x in names if x != n) for n in names] + ['off'])
-    sets = [None if v == 'off' else tuple(names) if v == 'all' else tuple(v.split('+')) for v in variants]
+    if variants == ['lag']:
+        variants = ['off', 'qkv+attn+o+gu', 'qkv+attn+o+gu+down_next', 'down_next', 'all', 'off']
+    toks = [() if v == 'off' else tuple(names) if v == 'all' else tuple(v.split('+')) for v in variants]
+    assert all(t in COHOST_PAIRS or t in LAG_TOKENS for ts in toks for t in ts), 'unknown pair'
+    # a variant = (pairs on | None for the un-hosted schedule, lagged guests)
+    sets = [(None if v == 'off' else tuple(t for t in ts if t in COHOST_PAIRS), tuple(LAG_TOKENS[t] for t in ts if t in LAG_TOKENS)) for v, ts in zip(variants, toks)]
     rounds, n = int(os.environ.get('AB_ROUNDS', 9)), 20
     torch.set_grad_enabled(False)
     vla = C.VLAConfig(base=C.vlaser_2b())
@@ -36,7 +44,7 @@ def main():
     call = lambda: m.infer_action(ids_d, pv_d, proprios=pro_d, noise=noise_d, valid_len=valid)
     graphs, ref = [], None
     for v, s in zip(variants, sets):
-        m.cohost_pairs, m._graphs = s, {}
+        (m.cohost_pairs, m.cohost_lagged), m._graphs = s, {}
         for _ in range(3):
             o = call()
         torch.cuda.synchronize()
@@ -46,7 +54,7 @@ def main():
     times = [[] for _ in variants]
     for r in range(rounds):
         for i, s in enumerate(sets):
-            m.cohost_pairs, m._graphs = s, graphs[i]
+            (m.cohost_pairs, m.cohost_lagged), m._graphs = s, graphs[i]
             call()
             torch.cuda.synchronize()
             t0 = time.perf_counter()

@@ -91,6 +91,7 @@ _SIGS = {
     'vlaser_chain_oproj': [C.POINTER(SkinnyArgs), vp],
     'vlaser_chain_gu': [C.POINTER(SkinnyArgs), vp],
     'vlaser_chain_down': [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp],
+    'vlaser_chain_down_looped': [vp, i32, vp, vp, vp, i32, i32, i32, vp],
     'vlaser_chain_gu_w8_supported': [i32, i32, i32, i32, i32],
     'vlaser_chain_gu_w8': [C.POINTER(SkinnyArgs), vp],
     'vlaser_chain_down_w8_supported': [i32, i32, i32],

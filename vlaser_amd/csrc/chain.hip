@@ -323,6 +323,29 @@ VL_INTERNAL int vl_cohost_chain_down(const VlaserCohostGuest* g, ChainDownP* p, 
   *wgs = vlaser_chain_down_geometry(a->N, &cols, &groups);
   return (a->M + 3) / 4 == 2 && cols == 3 && groups == 1;
 }
+// the looped form (chain_down_loop_kernel / GuestChainDown4): the same shape, and a workgroup count that four divides; *wgs = workgroups of four units
+VL_INTERNAL int vl_cohost_chain_down4(const VlaserCohostGuest* g, ChainDownP* p, int* wgs) {
+  int units;
+  if (!vl_cohost_chain_down(g, p, &units) || units % GuestChainDown4::UNITS) return 0;
+  *wgs = units / GuestChainDown4::UNITS;
+  return 1;
+}
+/* vlaser_chain_down at the shape the looped form is built for (M in 5..8, cols 3, one group, workgroups a multiple of 4, bf16 weights), run by the looped kernel on its
+   own: a quarter of the workgroups, four units each -- what the guest workgroups of the co-hosted q/k/v GEMM run.  Bit-identical to vlaser_chain_down.  Tests and tools. */
+extern "C" int vlaser_chain_down_looped(const void* x, int ldx, const void* W, const void* res, void* h_out, int M, int N, int K, vl_stream_t s) {
+  VlaserChainDownArgs a = {x, ldx, W, res, h_out, M, N, K, nullptr};
+  const VlaserCohostGuest g = {VL_GUEST_CHAIN_DOWN, &a};
+  ChainDownP p;
+  int wgs;
+  if (!vl_cohost_chain_down4(&g, &p, &wgs)) {
+    if (chain_down_prepare(x, ldx, W, nullptr, res, h_out, M, N, K, nullptr, false, p)) return -1;      // (its message)
+    vlaser_set_error("vlaser_chain_down_looped: built for 5..8 rows, 3-column units, a workgroup count that 4 divides (got M %d N %d)", M, N);
+    return -1;
+  }
+  hipLaunchKernelGGL((chain_down_loop_kernel<7, 10, 2, 3, 1, GuestChainDown4::UNITS>), dim3(wgs), dim3(7 * 64), 0, (hipStream_t)s, p);
+  VL_LAUNCH_CHECK();
+  return 0;
+}
 VL_INTERNAL int vl_cohost_guest_launch(const VlaserCohostGuest* g, vl_stream_t s) {
   if (!g || g->kind == VL_GUEST_NONE) return 0;
   VL_CHECK(g->args, "co-hosted launch: guest kind %d without arguments", g->kind);

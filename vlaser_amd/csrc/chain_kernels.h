@@ -157,6 +157,23 @@ __global__ __launch_bounds__(NW * 64) void chain_down_kernel(ChainDownP p) {
 #undef VL_GRID_Y
 }
 
+// The looped form (chain_down_loop.inc): workgroup wg does the work of the stand-alone launch's workgroups wg * UNITS .. + UNITS - 1 -- the activation slices, which
+// every one of those reads alike, requested once, the weights of unit u + 1 in flight under unit u's MFMAs.  Built for a launch that has few CUs to itself: the guest of
+// the joint prefill's q/k/v GEMM (GuestChainDown4 below: 64 idle CUs, one workgroup each because the fused launch carries the host's 128 KB LDS request; four rounds of
+// the stand-alone geometry there would outlast the host).  Bit-identical to chain_down_kernel; bf16 weights, CG = 1.
+template <int NW, int NL, int RG, int COLS, int CG, int UNITS>
+__device__ __forceinline__ void chain_down_loop_body(const ChainDownP& p, const int wg) {
+#define VL_WG_X wg
+#include "chain_down_loop.inc"
+#undef VL_WG_X
+}
+template <int NW, int NL, int RG, int COLS, int CG, int UNITS>
+__global__ __launch_bounds__(NW * 64) void chain_down_loop_kernel(ChainDownP p) {      // the looped body on its own (vlaser_chain_down_looped: tests, tools)
+#define VL_WG_X blockIdx.x
+#include "chain_down_loop.inc"
+#undef VL_WG_X
+}
+
 // ------------------------------------------------------------------------------------------------------------------ attention over the KV cache, <= 16 query tokens
 // One WAVE per (kv head, key split, 16-row tile, batch element), NC 32-key chunks each, no LDS, no barrier: Q of the tile's (q head, token) rows (the kv head has
 // <= 32 rows = two MFMA tiles), then K and V^T of every chunk of the wave are requested in one burst (vlaser_attn_skinny staged the same work through 4-wave workgroups whose merge
@@ -270,6 +287,15 @@ struct GuestChainDown {
   static constexpr int THREADS = 7 * 64;
   static __device__ __forceinline__ void run(const P& p, int gwg) { chain_down_body<7, 10, 2, 3, 1, false>(p, gwg); }
 };
+// the down projection as the guest of the NEXT layer's q/k/v GEMM (7 waves against the host's 4: the fused kernel's block is the guest's): four units per workgroup
+struct GuestChainDown4 {
+  typedef ChainDownP P;
+  static constexpr int THREADS = 7 * 64, UNITS = 4;
+  static __device__ __forceinline__ void run(const P& p, int gwg) {
+    if ((gwg + 1) * (UNITS * 3) > p.N) return;          // (a grid rounded up past the guest's workgroups)
+    chain_down_loop_body<7, 10, 2, 3, 1, UNITS>(p, gwg);
+  }
+};
 // one-wave bodies: ONE wave per guest workgroup, the stand-alone launch's geometry (the host's other waves return at once).  Several to a workgroup were measured and
 // lost: eight chain_attn waves pull 256 KB of K / V^T through one CU and outlast the o_proj GEMM (profiles/cohost_ab.md)
 struct GuestChainAttn {
@@ -298,6 +324,7 @@ VL_INTERNAL int vl_cohost_chain_qkv(const VlaserCohostGuest* g, ChainQkvP* p, in
 VL_INTERNAL int vl_cohost_chain_attn(const VlaserCohostGuest* g, ChainAttnP* p, int* waves);
 VL_INTERNAL int vl_cohost_chain_oproj(const VlaserCohostGuest* g, ChainOprojP* p, int* wgs, int* lds);
 VL_INTERNAL int vl_cohost_chain_down(const VlaserCohostGuest* g, ChainDownP* p, int* wgs);
+VL_INTERNAL int vl_cohost_chain_down4(const VlaserCohostGuest* g, ChainDownP* p, int* wgs);      // the looped form: *wgs = workgroups of four units
 VL_INTERNAL int vl_cohost_guest_launch(const VlaserCohostGuest* g, vl_stream_t s);      // the guest on its own, behind its host: what every pair without a fused instantiation does
 VL_INTERNAL void vl_cohost_count_fused();          // one more launch that carried its guest (vlaser_cohost_fused_count)
 VL_INTERNAL bool vl_cohost_lab_zero_guests();      // vlaser_cohost_lab(1): fused kernels launched with no guest workgroups

@@ -847,12 +847,13 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmP p) {
 
 // Co-hosted launch (csrc/chain_kernels.h): the host's grid, its x extent lengthened by the guest's workgroups.  Workgroups bx < host_grid are the GEMM's (tile index and
 // XCD remap over host_grid, NOT gridDim.x); the rest run guest workgroup (bx - host_grid) * gridDim.y + blockIdx.y -- the split-K copies of the appended x range all
-// carry guest work.  Block = the host's; dynamic LDS = the larger request (both hosts built here ask for > 80 KB: one workgroup per CU, a guest only lands on a CU
-// the host left idle or has already left).
+// carry guest work.  Block = the larger of the two bodies' (the 4-wave q/k/v tile carries the 7-wave down projection); the waves a body does not have return at once (a
+// terminated wave no longer counts at s_barrier).  Dynamic LDS = the larger request (the hosts built here ask for > 80 KB: one workgroup per CU, a guest only lands on
+// a CU the host left idle or has already left).
 template <class G, int EPI, int BM, int BNT, int WM, int WN, int NST, bool WKM, bool AKM, bool IFIRST, bool ASYM, bool SPREAD, bool PIPE>
-__global__ __launch_bounds__(WM * WN * 64) void gemm_glds_cohost_kernel(GemmP p, typename G::P gp, int host_grid) {
-  static_assert(G::THREADS <= WM * WN * 64, "the guest's block must fit the host's");
+__global__ __launch_bounds__(G::THREADS > WM * WN * 64 ? G::THREADS : WM * WN * 64) void gemm_glds_cohost_kernel(GemmP p, typename G::P gp, int host_grid) {
   if ((int)blockIdx.x < host_grid) {
+    if constexpr (G::THREADS > WM * WN * 64) { if ((int)threadIdx.x >= WM * WN * 64) return; }
     gemm_glds_body<EPI, BM, BNT, WM, WN, NST, WKM, AKM, IFIRST, ASYM, SPREAD, PIPE>(p, blockIdx.x, host_grid);
   } else {
     if constexpr (G::THREADS < WM * WN * 64) { if ((int)threadIdx.x >= G::THREADS) return; }
@@ -1029,7 +1030,7 @@ static int launch_glds_cohost(const VlaserGemmArgs* args, hipStream_t stream, in
   // host's own is, so that every y slice starts on XCD 0 (the guest bounds-checks its index)
   int gx = host_grid + (guest_wgs + splits - 1) / splits;
   if (splits > 1 && host_grid % 8 == 0) gx = (gx + 7) & ~7;
-  hipLaunchKernelGGL(kernel, dim3(gx, splits, 1), dim3(WM * WN * 64), lds, stream, p, gp, host_grid);
+  hipLaunchKernelGGL(kernel, dim3(gx, splits, 1), dim3(G::THREADS > WM * WN * 64 ? G::THREADS : WM * WN * 64), lds, stream, p, gp, host_grid);
   VL_LAUNCH_CHECK();
   vl_cohost_count_fused();
   return 0;
@@ -1129,10 +1130,17 @@ static int launch(const VlaserGemmArgs* args, hipStream_t stream, const VlaserCo
     vlaser_set_error("vlaser_gemm_tn_lds: force_cfg = %d is not a configuration code of the TN form (see the table at force_bm in include/vlaser_hip.h)", bm);
     return -1;
   }
-  if constexpr (!WKM && !AKM && (EPI == VL_EPI_SWIGLU || EPI == VL_EPI_PARTIAL)) {
-    // the two fused instantiations: the joint prefill's gate/up (128x256, 210 of 256 CUs) with the expert's gate/up, its o_proj (64x128, 3 K-splits, 216 CUs) with the expert's attention
+  if constexpr (!WKM && !AKM && (EPI == VL_EPI_SWIGLU || EPI == VL_EPI_PARTIAL || EPI == VL_EPI_QKV_ROPE)) {
+    // the fused instantiations: the joint prefill's gate/up (128x256, 210 of 256 CUs) with the expert's gate/up, its o_proj (64x128, 3 K-splits, 216 CUs) with the expert's
+    // attention, its q/k/v (64x64, 192 CUs) with the PREVIOUS expert layer's down projection in the looped form (64 workgroups of four units: one per idle CU)
     if (guest && hosted && nb == 1) {
-      if constexpr (EPI == VL_EPI_SWIGLU) {
+      if constexpr (EPI == VL_EPI_QKV_ROPE) {
+        ChainDownP gp; int wgs;
+        if (bm == 1564 && blocks(64, 64) <= 192 && vl_cohost_chain_down4(guest, &gp, &wgs)) {
+          *hosted = 1;
+          return launch_glds_cohost<GuestChainDown4, EPI, 64, 64, 2, 2, 8, PIPE>(args, stream, splits, gp, wgs, 0);
+        }
+      } else if constexpr (EPI == VL_EPI_SWIGLU) {
         ChainGuP gp; int wgs, lds;
         if (bm == 1200 && vl_cohost_chain_gu(guest, &gp, &wgs, &lds)) {
           *hosted = 1;
@@ -1444,7 +1452,7 @@ static int gemm_entry(int epi, const VlaserGemmArgs* a, const VlaserCohostGuest*
       VL_CHECK(a->q_out && a->k_cache && a->vt_cache && a->rope_cos && a->rope_sin && a->pos_ids && a->bias, "qkv_rope: null pointer");
       VL_CHECK(a->N == (a->n_q_heads + 2 * a->n_kv_heads) * 128, "qkv_rope: N mismatch");
       VL_CHECK(a->tok_per_batch > 0 && a->s_max > 0, "qkv_rope: bad cache geometry");
-      return launch<VL_EPI_QKV_ROPE>(a, stream);
+      return launch<VL_EPI_QKV_ROPE>(a, stream, guest, hosted);
     case VL_EPI_VIT_QKV:
       VL_CHECK(a->vq && a->vk && a->vvt && a->bias, "vit_qkv: null pointer");
       VL_CHECK(a->N == 3 * a->vit_heads * 64 && a->vit_seq > 0 && a->vit_seq_pad >= a->vit_seq, "vit_qkv: bad geometry");

@@ -543,6 +543,13 @@ def chain_down(x, W4, res, h_out, M, N, K, dbg=None, stream=None):
                                       _stream() if stream is None else stream), 'vlaser_chain_down')
 
 
+def chain_down_looped(x, W4, res, h_out, M, N, K, stream=None):
+    """chain_down by the looped kernel (four of its workgroups to one: the guest body of the co-hosted q/k/v GEMM) as a launch of its own; the same bits."""
+    assert x.dtype == BF16 and res.dtype == BF16 and h_out.dtype == BF16 and x.stride(-1) == 1 and res.data_ptr() != h_out.data_ptr()
+    L.check(L.lib().vlaser_chain_down_looped(x.data_ptr(), x.stride(0), W4.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K, _stream() if stream is None else stream),
+            'vlaser_chain_down_looped')
+
+
 # measured on the action-expert chunk: 72 / 100 / 130 / 160 target blocks -> 16.63 / 16.52 / 16.48 / 16.50 ms
 SK_TARGET_BLOCKS = 130
 

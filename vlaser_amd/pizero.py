@@ -114,33 +114,44 @@ def stage_pixels(pixel_values, out, dev):
 COHOST_PAIRS = {'qkv': 'attn', 'attn': 'o', 'o': 'seam_o', 'gu': 'gu', 'down': 'seam_d'}
 
 
-def cohost_plan(hosts, guests, enabled=tuple(COHOST_PAIRS)):
+# Lagged pairs (guest -> host launch of the NEXT VLM layer), chosen per call with cohost_plan's `lagged`: the expert's down projection of layer l in the q/k/v GEMM of VLM
+# layer l + 1 (192 workgroups of one per CU: 64 CUs idle for the whole launch; csrc/chain_kernels.h, GuestChainDown4).  Option token: LAG_TOKENS.
+COHOST_LAGGED = {'down': 'qkv'}
+LAG_TOKENS = {'down_next': 'down'}
+
+
+def cohost_plan(hosts, guests, enabled=tuple(COHOST_PAIRS), lagged=()):
     """The launch order of the co-hosted joint prefill, from the two launch lists alone (no tensors): hosts = [(layer, name)] of the prefill in launch order, guests =
-    [(layer, name)] of the expert's first pass in launch order, enabled = the guest names whose pair is switched on.  Returns [(host | None, guest | None)] in issue
-    order: (host, guest) = one co-hosted launch, (host, None) = the host alone, (None, guest) = the guest as a launch of its own.
+    [(layer, name)] of the expert's first pass in launch order, enabled = the guest names whose pair is switched on, lagged = the guest names that ride one VLM layer
+    later instead (COHOST_LAGGED).  Returns [(host | None, guest | None)] in issue order: (host, guest) = one co-hosted launch, (host, None) = the host alone,
+    (None, guest) = the guest as a launch of its own.
     A guest rides in the launch COHOST_PAIRS names, of its own layer.  A guest whose pair is off, or whose layer has no such launch (the last VLM layer stops after its
     q/k/v GEMM), is launched on its own directly behind that host -- behind its layer's q/k/v GEMM where the host does not exist -- and never in front of an earlier
-    guest: the expert's launches keep their order, every one of them is issued exactly once, and none before the q/k/v GEMM that writes the prefix keys it reads."""
+    guest: the expert's launches keep their order, every one of them is issued exactly once, and none before the q/k/v GEMM that writes the prefix keys it reads.
+    A lagged guest of layer l rides in the launch COHOST_LAGGED names of layer l + 1, whether or not its own pair is on, and the guests behind it wait for it; where layer
+    l + 1 has no such launch (the expert's last layer) it is placed as if it were not lagged."""
     hosts, guests = list(hosts), list(guests)
     where = {h: i for i, h in enumerate(hosts)}
+
+    def target(g):          # (index of the launch the guest rides in or runs behind, whether it rides)
+        gl, gn = g
+        if gn in lagged:
+            at = where.get((gl + 1, COHOST_LAGGED.get(gn)))
+            if at is not None:
+                return at, True
+        at = where.get((gl, COHOST_PAIRS.get(gn)))      # (a launch name without a pair -- a stack off the chain path -- has no host)
+        if at is None:
+            return where.get((gl, 'qkv'), -1), False
+        return at, gn in enabled
+
     out, gi = [], 0
     for hi, host in enumerate(hosts):
         paired = None
-        if gi < len(guests):
-            gl, gn = guests[gi]
-            if gn in enabled and (gl, COHOST_PAIRS.get(gn)) == host:
-                paired = guests[gi]
-                gi += 1
+        if gi < len(guests) and target(guests[gi]) == (hi, True):
+            paired = guests[gi]
+            gi += 1
         out.append((host, paired))
-        while gi < len(guests):          # guests that no later launch will carry and whose inputs are complete
-            gl, gn = guests[gi]
-            at = where.get((gl, COHOST_PAIRS.get(gn)))      # (a launch name without a pair -- a stack off the chain path -- has no host)
-            if at is None:
-                at = where.get((gl, 'qkv'), -1)
-            elif gn in enabled and at > hi:
-                break                    # its host is still to come
-            if at > hi:
-                break
+        while gi < len(guests) and target(guests[gi])[0] <= hi:          # guests that no later launch will carry and whose inputs are complete
             out.append((None, guests[gi]))
             gi += 1
     out += [(None, g) for g in guests[gi:]]
@@ -198,7 +209,11 @@ class PiZero:
     #          'cohost' = every pair; 'cohost=qkv+gu' = only those pairs ride, the other guests run as launches of their own behind their hosts.  profiles/cohost_ab.md
     #          ON for the four pairs that pass the per-pair A/B (tools/micro/cohost_ab.py, one model instance): qkv, attn, o, gu; hosting the down projection in the second seam
     #          is worth 0.04-0.05 ms, less than the 0.06 ms run-to-run spread of that job, and stays opt-in ('cohost' = all five)
-    EULER_DEFAULT = 'qkv16,gu16,glue1,chain,cohost=qkv+attn+o+gu'      # (gu16 ON with chain since r05: 224 workgroups x 5 units instead of 187 x 3, 11.79 -> 11.68 ms per chunk, same-box A/B)
+    #          'down_next' among the pairs (not together with 'down'): the down projection of expert layer l rides in the q/k/v GEMM of VLM layer l + 1 instead
+    #          (COHOST_LAGGED; 192 workgroups of one per CU leave 64 CUs idle for 12 us), run there by the looped body -- 64 workgroups of four units, the activations
+    #          requested once (csrc/chain_down_loop.inc).  The fused launch lasts 12.75 us against the host's 11.97, and a 6.7 us launch leaves the chain 27 times:
+    #          -0.14 ms per chunk in the set, -0.16 ms alone, against a 0.07 ms spread; bench.py 11.087 -> 10.935 ms.  ON.  profiles/cohost_lag_ab.md
+    EULER_DEFAULT = 'qkv16,gu16,glue1,chain,cohost=qkv+attn+o+gu+down_next'      # (gu16 ON with chain since r05: 224 workgroups x 5 units instead of 187 x 3, 11.79 -> 11.68 ms per chunk, same-box A/B)
 
     ERR_BITS = {1: 'image_text_proprio_mask: the keys the proprio row sees are not a contiguous valid prefix',
                 2: 'image_text_proprio_mask: a valid-prefix row (or the proprio row\'s own key) does not have the prefix pattern of build_causal_mask_and_position_ids',
@@ -246,15 +261,20 @@ class PiZero:
                 raise ValueError(f"Euler option 'mlp8' (expert_mlp_weights='fp8') needs {', '.join(missing)}: the e4m3 MLP weights are read by the chain kernels' 16-row-unit forms only")
         self.expert_mlp_weights = 'fp8' if 'mlp8' in self.euler_opts else 'bf16'
         # 'cohost' / 'cohost=a+b': the pairs of the co-hosted joint prefill that are switched on (None: the option is off)
-        self.cohost_pairs = None
+        # cohost_lagged: the guests that ride one VLM layer later ('down_next': COHOST_LAGGED)
+        self.cohost_pairs, self.cohost_lagged = None, ()
         for o in self.euler_opts:
             if o == 'cohost' or o.startswith('cohost='):
                 pairs = tuple(COHOST_PAIRS) if o == 'cohost' else tuple(x for x in o[len('cohost='):].split('+') if x)
-                bad = [x for x in pairs if x not in COHOST_PAIRS]
+                bad = [x for x in pairs if x not in COHOST_PAIRS and x not in LAG_TOKENS]
                 missing = [x for x in ('chain', 'qkv16', 'gu16', 'glue1') if x not in self.euler_opts]
                 if bad or missing:
-                    raise ValueError(f"Euler option {o!r}: " + (f"unknown pair(s) {', '.join(bad)} (of {', '.join(COHOST_PAIRS)})" if bad else f"needs {', '.join(missing)}"))
-                self.cohost_pairs = pairs
+                    raise ValueError(f"Euler option {o!r}: " + (f"unknown pair(s) {', '.join(bad)} (of {', '.join((*COHOST_PAIRS, *LAG_TOKENS))})" if bad else f"needs {', '.join(missing)}"))
+                both = [x for x in pairs if x in LAG_TOKENS and LAG_TOKENS[x] in pairs]
+                if both:
+                    raise ValueError(f"Euler option {o!r}: {both[0]} and {LAG_TOKENS[both[0]]} are two places for one launch: name one of them")
+                self.cohost_pairs = tuple(x for x in pairs if x in COHOST_PAIRS)
+                self.cohost_lagged = tuple(LAG_TOKENS[x] for x in pairs if x in LAG_TOKENS)
         self._graphs = {}
         self._pos_state = None
         self._pos_next = None
@@ -416,6 +436,11 @@ class PiZero:
               T .. T + 4 that its own q/k/v wrote one launch earlier.
           (c) host and guest of every pair write disjoint buffers: pbuf.*, h_vlm, pbuf.part and the cache slots < T against sb_pro.* and the slots >= T; valid_len is
               read by both and written by neither.
+          (d) 'down_next': the expert's down projection of layer l rides in the q/k/v GEMM of VLM layer l + 1 (the last VLM layer's q/k/v GEMM hosts layer nL - 2; expert
+              layer nL - 1 runs un-hosted).  That host reads the pbuf activations the second seam of layer l wrote, and writes pbuf q/k/v and the cache slots < T of
+              layer l + 1.  The guest reads the expert's gate/up output and residual (sb_pro.act, sb_pro.hB), written two or more launches earlier by the expert's
+              gate/up of layer l, and writes only the expert's residual stream (sb_pro.hC).  The first reader of that stream, the expert's q/k/v of layer l + 1, rides
+              one launch later in the attention (or runs behind it); the stream's previous readers, the expert's q/k/v and gate/up of layer l, finished launches ago.
         The proprio encoder and the action encoder of step 0 depend on the call's inputs only and go first."""
         cfg = self.cfg
         llm, ex = cfg.base.llm, cfg.expert
@@ -446,7 +471,7 @@ class PiZero:
         hostable = all(p.chain and p.chain_ao for p in plans)      # (a stack off the chain path has other launches: they all run on their own, in order)
         stream = torch.cuda.current_stream().cuda_stream
         prefill_begin(self.vlm, self.pbuf, h_vlm, B * T)
-        for host, guest in cohost_plan(hosts, guests, self.cohost_pairs if hostable else ()):
+        for host, guest in cohost_plan(hosts, guests, self.cohost_pairs if hostable else (), self.cohost_lagged if hostable else ()):
             if host is None:
                 _, launch, args = next(l for l in plans[guest[0]].launches if l[0] == guest[1])
                 launch(*args, stream)
