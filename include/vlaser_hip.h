@@ -226,7 +226,7 @@ typedef struct {
   /* VL_PRO_ATTN: x[m = b*nq+tok][h*128+d] = sum_s o_s e^(m_s-M) / sum_s l_s e^(m_s-M) */
   const float* attn_m; const float* attn_l; const float* attn_o; int attn_splits, attn_group, attn_nq;
   unsigned long long* dbg; /* optional: per-block timestamps [grid][8] (wall_clock64, 100 MHz) for kernel tuning */
-  const float* w_scale;    /* vlaser_chain_gu_w8 only (appended, ABI 8 unchanged: nothing else reads it): fp32 [N] row scales of the e4m3 weights, in the packed row order of W */
+  const float* w_scale;    /* vlaser_chain_gu_w8 / _w8_k1536 only (appended, ABI 8 unchanged: nothing else reads it): fp32 [N] row scales of the e4m3 weights, in the packed row order of W */
 } VlaserSkinnyArgs;
 
 int vlaser_skinny(int prologue, int epi, const VlaserSkinnyArgs* args, vl_stream_t stream);
@@ -273,6 +273,11 @@ int vlaser_chain_gu_w8_supported(int M, int N, int K, int n_partials, int tiles_
 int vlaser_chain_gu_w8(const VlaserSkinnyArgs* args, vl_stream_t stream);
 int vlaser_chain_down_w8_supported(int M, int N, int K);
 int vlaser_chain_down_w8(const void* x, int ldx, const void* W, const float* w_scale, const void* res, void* h_out, int M, int N, int K, unsigned long long* dbg, vl_stream_t stream);
+/* (ABI 8, additive) the gate/up W8 form at K = 1536, for the Vlaser-2B LLM's greedy decode (VLASER_DECODE_OPTS=...,mlp8 / InternVLChatModel(llm_mlp_weights='fp8')): a pair of
+ * its own, the pair above answers exactly as before.  W = ops.pack_gate_up8_e4m3 at K = 1536: per unit and wave THREE blocks of 64 x 16 bytes, block j the lanes'
+ * fragments of K-steps 2j and 2j + 1 (3072 contiguous bytes, no 8-byte tail); 2 producer slabs, 5 units per workgroup, M <= 8.  vlaser_chain_down_w8 already serves N = 1536. */
+int vlaser_chain_gu_w8_k1536_supported(int M, int N, int K, int n_partials, int tiles_per_unit);
+int vlaser_chain_gu_w8_k1536(const VlaserSkinnyArgs* args, vl_stream_t stream);
 /* (ABI 8: four entry points left without a change of number, no struct and no remaining prototype changed: vlaser_chain_down2, vlaser_chain_down2_supported,
  * vlaser_chain_qkv2_supported -- the down projection as two K halves leaving fp32 slabs for q/k/v to fold, measured equal inside the chunk and never shipped --
  * and vlaser_chain_qkv_set_waves, a process-global switch that only that comparison needed.  profiles/HISTORY.md keeps the measurement.) */

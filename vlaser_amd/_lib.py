@@ -94,6 +94,8 @@ _SIGS = {
     'vlaser_chain_down_looped': [vp, i32, vp, vp, vp, i32, i32, i32, vp],
     'vlaser_chain_gu_w8_supported': [i32, i32, i32, i32, i32],
     'vlaser_chain_gu_w8': [C.POINTER(SkinnyArgs), vp],
+    'vlaser_chain_gu_w8_k1536_supported': [i32, i32, i32, i32, i32],
+    'vlaser_chain_gu_w8_k1536': [C.POINTER(SkinnyArgs), vp],
     'vlaser_chain_down_w8_supported': [i32, i32, i32],
     'vlaser_chain_down_w8': [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp],
     'vlaser_layernorm': [vp, vp, vp, vp, i32, i32, f32, vp],

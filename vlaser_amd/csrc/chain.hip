@@ -34,35 +34,44 @@ static int chain_gu_launch(const ChainGuP& p, int gx, int lds, hipStream_t strea
 
 /* tpu = tiles per unit of the packed weights (2: pack_gate_up, 1: pack_gate_up8).
    ONE list of the built variants {K / 256, units per workgroup, producer slabs, tiles per unit} per weight format: the predicates and the dispatch below are generated from
-   them (the predicate admitted K = 768 / 2 slabs / 2 units per workgroup, which has no instantiation).  The e4m3 list holds what the action expert reaches. */
+   them (the predicate admitted K = 768 / 2 slabs / 2 units per workgroup, which has no instantiation).  The e4m3 list holds what the action expert reaches,
+   the second e4m3 list (the vlaser_chain_gu_w8_k1536 pair) what the Vlaser-2B greedy decode reaches.  fmt: 0 = bf16, 1 = e4m3, 2 = e4m3 at K = 1536. */
 #define CG_VARIANTS(X) X(3, 3, 3, 2) X(3, 3, 2, 2) X(6, 3, 2, 2) X(3, 2, 3, 2) X(6, 2, 2, 2) X(3, 5, 3, 1) X(6, 5, 2, 1)
 #define CG_W8_VARIANTS(X) X(3, 5, 3, 1)
-static int chain_gu_has(int M, int N, int K, int n_partials, int tpu, bool w8) {
+#define CG_W8_K1536_VARIANTS(X) X(6, 5, 2, 1)
+enum { CG_BF16 = 0, CG_W8 = 1, CG_W8_K1536 = 2 };
+static int chain_gu_has(int M, int N, int K, int n_partials, int tpu, int fmt) {
   if (M < 1 || M > 16 || K % 256 || (tpu != 1 && tpu != 2) || N < 16 * tpu || N % (16 * tpu)) return 0;
   const int cpt = (M * (K / 8) + 511) / 512;
   if (cpt > 3) return 0;
   const int ns = K / 256, units = N / (16 * tpu), longest = (units + 255) / 256;
 #define CG_HAS(NS_, UE_, SP_, TPU_) if (ns == NS_ && longest == UE_ && n_partials == SP_ && tpu == TPU_) return 1;
-  if (w8) { CG_W8_VARIANTS(CG_HAS) } else { CG_VARIANTS(CG_HAS) }
+  if (fmt == CG_W8_K1536) { CG_W8_K1536_VARIANTS(CG_HAS) } else if (fmt == CG_W8) { CG_W8_VARIANTS(CG_HAS) } else { CG_VARIANTS(CG_HAS) }
 #undef CG_HAS
   return 0;
 }
-extern "C" int vlaser_chain_gu_supported(int M, int N, int K, int n_partials, int tpu) { return chain_gu_has(M, N, K, n_partials, tpu, false); }
-extern "C" int vlaser_chain_gu_w8_supported(int M, int N, int K, int n_partials, int tpu) { return chain_gu_has(M, N, K, n_partials, tpu, true); }
+extern "C" int vlaser_chain_gu_supported(int M, int N, int K, int n_partials, int tpu) { return chain_gu_has(M, N, K, n_partials, tpu, CG_BF16); }
+extern "C" int vlaser_chain_gu_w8_supported(int M, int N, int K, int n_partials, int tpu) { return chain_gu_has(M, N, K, n_partials, tpu, CG_W8); }
+extern "C" int vlaser_chain_gu_w8_k1536_supported(int M, int N, int K, int n_partials, int tpu) { return chain_gu_has(M, N, K, n_partials, tpu, CG_W8_K1536); }
 
 struct ChainGuGeom { int gx, lds, ns, longest, cpt, tpu; };
 /* validation + kernel parameters + launch geometry of a vlaser_chain_gu call: what the stand-alone launch and a co-hosted one share */
-static int chain_gu_prepare(const VlaserSkinnyArgs* a, bool w8, ChainGuP& p, ChainGuGeom& q) {
+static int chain_gu_prepare(const VlaserSkinnyArgs* a, int fmt, ChainGuP& p, ChainGuGeom& q) {
+  const bool w8 = fmt != CG_BF16;
   VL_CHECK(a && a->x && a->W && a->norm_w && a->out && a->partials, "vlaser_chain_gu: null operand");
   VL_CHECK(!w8 || a->w_scale, "vlaser_chain_gu_w8: null w_scale (fp32 row scales of the e4m3 weights, packed row order)");
   const int tpu = a->tiles_per_unit == 1 ? 1 : 2;
   VL_CHECK(a->tiles_per_unit == 2 || a->tiles_per_unit == 0 || a->tiles_per_unit == 1, "vlaser_chain_gu: weights packed in 32-row (pack_gate_up) or 16-row (pack_gate_up8) units");
-  if (w8)
-    VL_CHECK(a->k_splits == 1 && chain_gu_has(a->M, a->N, a->K, a->n_partials, tpu, true),
+  if (fmt == CG_W8_K1536)
+    VL_CHECK(a->k_splits == 1 && chain_gu_has(a->M, a->N, a->K, a->n_partials, tpu, CG_W8_K1536),
+             "vlaser_chain_gu_w8_k1536: built for K = 1536, 2 producer slabs, 5 16-row units per workgroup, M <= 8 (got M %d N %d K %d slabs %d tiles per unit %d)", a->M, a->N, a->K,
+             a->n_partials, tpu);
+  else if (fmt == CG_W8)
+    VL_CHECK(a->k_splits == 1 && chain_gu_has(a->M, a->N, a->K, a->n_partials, tpu, CG_W8),
              "vlaser_chain_gu_w8: built for K = 768, 3 producer slabs, 5 16-row units per workgroup, M * K / 8 <= 1536 chunks (got M %d N %d K %d slabs %d tiles per unit %d)", a->M, a->N, a->K,
              a->n_partials, tpu);
   else
-    VL_CHECK(a->k_splits == 1 && chain_gu_has(a->M, a->N, a->K, a->n_partials, tpu, false),
+    VL_CHECK(a->k_splits == 1 && chain_gu_has(a->M, a->N, a->K, a->n_partials, tpu, CG_BF16),
              "vlaser_chain_gu: built for K = 768 / 1536, 2 or 3 producer slabs, 2-3 (32-row) or 5 (16-row) units per workgroup, M * K / 8 <= 1536 chunks (got M %d N %d K %d slabs %d)", a->M, a->N,
              a->K, a->n_partials);
   VL_CHECK(((uintptr_t)a->W & 15) == 0 && ((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->partials & 15) == 0 && ((uintptr_t)a->out & 7) == 0 && a->ldo % 4 == 0 &&
@@ -80,24 +89,25 @@ static int chain_gu_prepare(const VlaserSkinnyArgs* a, bool w8, ChainGuP& p, Cha
   return 0;
 }
 
-static int chain_gu_entry(const VlaserSkinnyArgs* a, vl_stream_t s, bool w8) {
+static int chain_gu_entry(const VlaserSkinnyArgs* a, vl_stream_t s, int fmt) {
   ChainGuP p;
   ChainGuGeom q;
-  if (int rc = chain_gu_prepare(a, w8, p, q)) return rc;
+  if (int rc = chain_gu_prepare(a, fmt, p, q)) return rc;
   const int ns = q.ns, longest = q.longest, cpt = q.cpt, tpu = q.tpu, gx = q.gx, lds = q.lds;
   hipStream_t stream = (hipStream_t)s;
 #define CG_CASE(NS_, UE_, SP_, CPT_, TPU_, W8_) if (ns == NS_ && longest == UE_ && a->n_partials == SP_ && cpt == CPT_ && tpu == TPU_) return chain_gu_launch<NS_, UE_, SP_, CPT_, TPU_, W8_>(p, gx, lds, stream);
 #define CG_CPT(NS_, UE_, SP_, TPU_) CG_CASE(NS_, UE_, SP_, 1, TPU_, false) CG_CASE(NS_, UE_, SP_, 2, TPU_, false) CG_CASE(NS_, UE_, SP_, 3, TPU_, false)
 #define CG_W8_CPT(NS_, UE_, SP_, TPU_) CG_CASE(NS_, UE_, SP_, 1, TPU_, true) CG_CASE(NS_, UE_, SP_, 2, TPU_, true) CG_CASE(NS_, UE_, SP_, 3, TPU_, true)
-  if (w8) { CG_W8_VARIANTS(CG_W8_CPT) } else { CG_VARIANTS(CG_CPT) }
+  if (fmt == CG_W8_K1536) { CG_W8_K1536_VARIANTS(CG_W8_CPT) } else if (fmt == CG_W8) { CG_W8_VARIANTS(CG_W8_CPT) } else { CG_VARIANTS(CG_CPT) }
 #undef CG_W8_CPT
 #undef CG_CPT
 #undef CG_CASE
   vlaser_set_error("vlaser_chain_gu: no variant for K %d, %d units per workgroup, %d slabs, %d chunks per thread, %d tiles per unit", a->K, longest, a->n_partials, cpt, tpu);
   return -1;
 }
-extern "C" int vlaser_chain_gu(const VlaserSkinnyArgs* a, vl_stream_t s) { return chain_gu_entry(a, s, false); }
-extern "C" int vlaser_chain_gu_w8(const VlaserSkinnyArgs* a, vl_stream_t s) { return chain_gu_entry(a, s, true); }
+extern "C" int vlaser_chain_gu(const VlaserSkinnyArgs* a, vl_stream_t s) { return chain_gu_entry(a, s, CG_BF16); }
+extern "C" int vlaser_chain_gu_w8(const VlaserSkinnyArgs* a, vl_stream_t s) { return chain_gu_entry(a, s, CG_W8); }
+extern "C" int vlaser_chain_gu_w8_k1536(const VlaserSkinnyArgs* a, vl_stream_t s) { return chain_gu_entry(a, s, CG_W8_K1536); }
 
 
 extern "C" int vlaser_chain_qkv_supported(int M, int N, int K) { return M >= 1 && ((K == 768 && M <= 16) || (K == 1536 && M <= 8)) && N % 128 == 0; }      // (hidden 1536 x 16 rows would spill)
@@ -286,7 +296,7 @@ VL_INTERNAL int vl_cohost_chain_gu(const VlaserCohostGuest* g, ChainGuP* p, int*
   if (!g || g->kind != VL_GUEST_CHAIN_GU || !g->args) return 0;
   const VlaserSkinnyArgs* a = (const VlaserSkinnyArgs*)g->args;
   ChainGuGeom q;
-  if (a->dbg || chain_gu_prepare(a, false, *p, q)) return 0;
+  if (a->dbg || chain_gu_prepare(a, CG_BF16, *p, q)) return 0;
   if (!(q.ns == 3 && q.longest == 5 && a->n_partials == 3 && q.cpt == 1 && q.tpu == 1)) return 0;
   *wgs = q.gx; *lds = q.lds;
   return 1;

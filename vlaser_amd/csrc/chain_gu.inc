@@ -1,7 +1,7 @@
 // Body of chain_gu_kernel: included where VL_WG_X / VL_WG_Y / VL_WG_Z (the workgroup's place in its logical grid) and VL_GRID_X / VL_GRID_Y (that grid)
 // are defined -- blockIdx / gridDim in the stand-alone kernel, arguments where the body runs as part of a co-hosted launch.  The text is the kernel's, so the
 // stand-alone kernel compiles to what it was.
-  static_assert(!W8 || (NS == 3 && TPU == 1), "e4m3 weights: built for K = 768 and 16-row units");
+  static_assert(!W8 || (TPU == 1 && (NS == 3 || NS == 6)), "e4m3 weights: built for K = 768 / 1536 and 16-row units");
   constexpr int K = NS * 256, cpr = K / 8, ngr = cpr / 16, gstride = (ngr + 3) & ~3, XS = K * 2 + 16, NF = TPU * NS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, g = lane >> 4;
@@ -45,15 +45,18 @@
   // instead of 2.3).  The barrier waits for instruction issue only -- nobody waits for data here.
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
-  u32x4 w[UE][W8 ? 1 : NF];
-  u32x2 w2[W8 ? UE : 1];
+  // W8: NP 16-byte loads, each the lane's fragments of K-steps 2j and 2j + 1, then (odd NS: K = 768) one 8-byte load of the last K-step -- WB bytes per wave and unit
+  constexpr int NP = NS / 2, WB = NS * 512;
+  u32x4 w[UE][W8 ? NP : NF];
+  u32x2 w2[W8 ? UE : 1];          // (even NS: never read)
   if constexpr (W8) {
-    const char* wp = reinterpret_cast<const char*>(p.W) + (size_t)wave * 1536;
+    const char* wp = reinterpret_cast<const char*>(p.W) + (size_t)wave * WB;
 #pragma unroll
     for (int u = 0; u < UE; ++u) {
-      const char* src = wp + (size_t)(ustart + min(u, ucount - 1)) * (8 * 1536);           // a workgroup with fewer units re-requests its last one
-      w[u][0] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src) + lane);
-      w2[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(src + 1024) + lane);
+      const char* src = wp + (size_t)(ustart + min(u, ucount - 1)) * (8 * WB);           // a workgroup with fewer units re-requests its last one
+#pragma unroll
+      for (int j = 0; j < NP; ++j) w[u][j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src + j * 1024) + lane);
+      if constexpr (NS & 1) w2[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(src + NP * 1024) + lane);
       __builtin_amdgcn_sched_barrier(0);
     }
   } else {
@@ -131,7 +134,7 @@
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         if constexpr (W8) {
-          a0 = mfma16(as_bf16x8(s < 2 ? ch_e4m3x8(w[u][0][2 * (s & 1)], w[u][0][2 * (s & 1) + 1]) : ch_e4m3x8(w2[u][0], w2[u][1])), xf[s], a0);
+          a0 = mfma16(as_bf16x8(s < 2 * NP ? ch_e4m3x8(w[u][s >> 1][2 * (s & 1)], w[u][s >> 1][2 * (s & 1) + 1]) : ch_e4m3x8(w2[u][0], w2[u][1])), xf[s], a0);
         } else {
           a0 = mfma16(as_bf16x8(w[u][TPU * s]), xf[s], a0);
           if constexpr (TPU == 2) a1 = mfma16(as_bf16x8(w[u][2 * s + 1]), xf[s], a1);

@@ -35,7 +35,9 @@ struct ChainGuP {
 // [gate 2g, gate 2g+1, up 2g, up 2g+1] of the unit's 8 activation columns (ops.pack_gate_up8: 1120 instead of 560 units -> 224 workgroups x 5 instead of 187 x 3)
 // W8: the unit's weights as e4m3 codes (ops.pack_gate_up8_e4m3).  K = 768 leaves a wave 3 K-steps = 24 bytes per lane and unit: ONE 16-byte load carries the lane's
 // fragments of K-steps 0 and 1, ONE 8-byte load the fragment of K-step 2 (a wave's unit = 64 x 16 bytes, then 64 x 8 bytes: 1536 contiguous bytes) -- two requests per
-// unit instead of three, the same (row, k) elements in every lane, consumed in the same order.
+// unit instead of three, the same (row, k) elements in every lane, consumed in the same order.  K = 1536 (the Vlaser-2B LLM) leaves a wave 6 K-steps = 48 bytes per lane
+// and unit: THREE 16-byte loads, load j the lane's fragments of K-steps 2j and 2j + 1 (a wave's unit = [j][lane][16 bytes] = 3072 contiguous bytes), no 8-byte tail;
+// w[UE][3] = 60 VGPRs at UE = 5 against the bf16 form's 120.
 template <int NS, int UE, int SP, int CPT, int TPU, bool DBG, bool W8 = false>
 __device__ __forceinline__ void chain_gu_body(const ChainGuP& p, const int wg) {
 #define VL_WG_X wg

@@ -37,15 +37,19 @@ class QwenLayerWeights:
         mlp8 = 'mlp8' in opts
         if mlp8:
             # 'mlp8': the MLP weights as e4m3 codes + power-of-two row scales (ops.quantize_rows_e4m3, on the host at load), in the packings of the W8 chain kernels; the
-            # bf16 packings below are read only by the launches those replace and are not built
+            # bf16 weight-streaming packings below are read only by the launches those replace and are not built.  A stack that also carries GEMM packings (the VLM's LLM:
+            # prefill and forward()) builds them from the DEQUANTISED weights -- exact in bf16 -- so that prefill, forward() and the decode compute one and the same model.
             H, I = llm.hidden_size, llm.intermediate_size
-            if gemm or not skinny or 'gu16' not in opts or not chain_packed(opts, H, I):
-                raise ValueError("'mlp8' serves the weight-streaming chain path only: needs 'chain', 'qkv16', 'gu16' and hidden 768 / MLP width 8960")
+            if not skinny or 'gu16' not in opts or not chain_packed(opts, H, I) or H not in (768, 1536):
+                raise ValueError("'mlp8' serves the weight-streaming chain path only: needs 'chain', 'qkv16', 'gu16', hidden 768 / 1536 and MLP width 8960")
             q = lambda k: ops.quantize_rows_e4m3(sd[p + k])
-            self.gu8 = ops.pack_gate_up8_e4m3(*q('mlp.gate_proj.weight'), *q('mlp.up_proj.weight')).to(device)
-            dc, ds = q('mlp.down_proj.weight')
+            (gc, gs), (uc, us), (dc, ds) = q('mlp.gate_proj.weight'), q('mlp.up_proj.weight'), q('mlp.down_proj.weight')
+            self.gu8 = ops.pack_gate_up8_e4m3(gc, gs, uc, us).to(device)
             self.down8, self.down8_scale = ops.pack_down4_e4m3(dc).to(device), ops.pack_down4_scales(ds).to(device)
             self.sk_gu = self.sk_down = None
+            if gemm:
+                dq = lambda c, sc: _dev(ops.dequantize_rows_e4m3(c, sc), device)
+                wgu, wdown = ops.pack_gate_up(dq(gc, gs), dq(uc, us)), dq(dc, ds)
         else:
             wgu = ops.pack_gate_up(g('mlp.gate_proj.weight'), g('mlp.up_proj.weight'))
             wdown = g('mlp.down_proj.weight')
@@ -121,13 +125,14 @@ def layer_path(*, chain_packed, H, I, n_qkv, n_gu, tpu_gu, n_o, tpu_o, ks_o, nq,
     A dense additive mask (ABI 8) is served by the chain attention only (every <= 16-row launch of the VLA at its shipped widths): NotImplementedError elsewhere.
     mlp8: the stack holds its MLP weights as e4m3 codes, which only the W8 forms of the chain gate/up and down kernels read: chain means those two launches, and a call
     that would run the MLP off the chain path raises NotImplementedError (a call that stops after q/k/v reads no MLP weight)."""
-    if mlp8:
-        mlp_ok = ops.chain_gu_w8_supported(M, n_gu, H, ks_o, tpu_gu) and ops.chain_down_w8_supported(M, H, I)
+    if mlp8:          # the gate/up W8 form has one predicate per K (hidden 1536: M <= 8)
+        gu_w8_supported = ops.chain_gu_w8_k1536_supported if H == 1536 else ops.chain_gu_w8_supported
+        mlp_ok = gu_w8_supported(M, n_gu, H, ks_o, tpu_gu) and ops.chain_down_w8_supported(M, H, I)
     else:
         mlp_ok = ops.chain_gu_supported(M, n_gu, H, ks_o, tpu_gu) and ops.chain_down_supported(M, H, I)
     chain = chain_packed and act_width == I and n_partials == 0 and not input_is_hB and ops.chain_qkv_supported(M, n_qkv, H) and mlp_ok
     if mlp8 and not chain and not skip_post_attn:
-        raise NotImplementedError("'mlp8' (e4m3 MLP weights) needs the chain path: hidden 768, MLP width 8960, <= 16 rows, an already reduced residual stream")
+        raise NotImplementedError("'mlp8' (e4m3 MLP weights) needs the chain path: hidden 768 (<= 16 rows) / 1536 (<= 8 rows), MLP width 8960, an already reduced residual stream")
     chain_ao = (chain and not skip_post_attn and tpu_o == 1 and tok_per_batch * (nq // nkv) <= 32
                 and ops.chain_oproj_supported(M, n_o, nq * hd, ks_o, ops.chain_attn_splits(kv_len), nq // nkv))
     if dense_mask and not (chain_ao or (chain and skip_post_attn)):
@@ -513,7 +518,7 @@ def _build_plan(stack, lw, sb, h_in, partials, n_partials, cache, layer, rope, p
     if chain:
         plan.down = SimpleNamespace(dbg=None)
         if mlp8:
-            plan.launches += [('gu', ops.launch_chain_gu_w8, (plan.gu[0],)), ('down', _chain_down_w8, (sb, lw, M, H, I, plan.down))]
+            plan.launches += [('gu', ops.launch_chain_gu_w8_k1536 if H == 1536 else ops.launch_chain_gu_w8, (plan.gu[0],)), ('down', _chain_down_w8, (sb, lw, M, H, I, plan.down))]
         else:
             plan.launches += [('gu', ops.launch_chain_gu, (plan.gu[0],)), ('down', _chain_down, (sb, lw.sk_down4, M, H, I, plan.down))]
         plan.result = (sb.hC, None, 0)

@@ -25,8 +25,36 @@ from .config import VlaserConfig
 from .engine import BF, KVCache, PrefillBuffers, QwenStack, SkinnyBuffers, VitEngine, prefill_begin, prefill_layer, skinny_layer
 
 
+DECODE_DEFAULT = 'qkv16,gu16,chain'      # VLASER_DECODE_OPTS at hidden 768 / 1536 (what the 16-row units and the chain kernels are built for); '' elsewhere
+
+
+def resolve_decode_opts(llm, llm_mlp_weights='bf16', env_value=None):
+    """(opts, decode_group) of the LLM stack: the decode options (env_value = the VLASER_DECODE_OPTS string, None = unset -> DECODE_DEFAULT at hidden 768 / 1536,
+    none elsewhere) with 'mlp8' added for llm_mlp_weights='fp8', and the number of sequences generate() decodes per group.  Pure: reads the config only, no GPU, no library.
+    'mlp8' (opt-in, off by default): the LLM's gate/up/down weights as OCP e4m3 codes with one power-of-two scale per row, quantised at load and streamed by the W8 forms
+    of the chain gate/up and down kernels (0.63 x the bytes of a decode step); prefill and forward() run their GEMMs on the dequantised weights, so the model computes
+    what the default model computes on dequantize(quantize(.)) of those six matrices per layer, bit for bit.  It is NOT the bf16 model: deviation on released checkpoints
+    unmeasured.  The chain kernels take <= 8 rows at hidden 1536 (16 at 768), and there is no other kernel that reads the codes: generate() groups by that."""
+    if llm_mlp_weights not in ('bf16', 'fp8'):
+        raise ValueError(f"llm_mlp_weights: 'bf16' or 'fp8', not {llm_mlp_weights!r}")
+    H, I = llm.hidden_size, llm.intermediate_size
+    raw = env_value if env_value is not None else (DECODE_DEFAULT if H in (768, 1536) else '')
+    opts = tuple(o for o in raw.split(',') if o and o != 'none')
+    if llm_mlp_weights == 'fp8' and 'mlp8' not in opts:
+        opts += ('mlp8',)
+    if 'mlp8' not in opts:
+        return opts, 16
+    if H not in (768, 1536) or I != ops.DOWN4_WAVES * ops.DOWN4_LOADS * 128:
+        raise ValueError(f"decode option 'mlp8' (llm_mlp_weights='fp8') is built for the chain kernels' widths, hidden 768 / 1536 with MLP width 8960 (Vlaser-2B); "
+                         f"hidden {H} / MLP width {I} (Vlaser-8B) decodes through the GEMM path, which has no e4m3 form")
+    missing = [o for o in ('chain', 'qkv16', 'gu16') if o not in opts]
+    if missing:
+        raise ValueError(f"decode option 'mlp8' (llm_mlp_weights='fp8') needs {', '.join(missing)}: the e4m3 MLP weights are read by the chain kernels' 16-row-unit forms only")
+    return opts, (8 if H == 1536 else 16)
+
+
 class InternVLChatModel:
-    def __init__(self, config: VlaserConfig, device='cuda', max_tiles=1, max_seq_len=1024, max_batch=1, decode_graph=True):
+    def __init__(self, config: VlaserConfig, device='cuda', max_tiles=1, max_seq_len=1024, max_batch=1, decode_graph=True, llm_mlp_weights='bf16'):
         L.lib()   # fail loudly when the HIP library is missing
         self.decode_graph = decode_graph          # uniform batches: greedy / sampled decode steps replayed from one HIP graph
         if not torch.cuda.is_available():
@@ -45,6 +73,9 @@ class InternVLChatModel:
         self._max_tiles, self._max_seq, self._max_batch = max_tiles, (max_seq_len + 63) // 64 * 64, max_batch
         self.vit = None
         self.llm = None
+        # llm_mlp_weights='fp8' (opt-in; the same as 'mlp8' in VLASER_DECODE_OPTS): resolve_decode_opts.  decode_group: sequences per decode group of generate()
+        self.decode_opts, self.decode_group = resolve_decode_opts(config.llm, llm_mlp_weights, os.environ.get('VLASER_DECODE_OPTS'))
+        self.llm_mlp_weights = 'fp8' if 'mlp8' in self.decode_opts else 'bf16'
         if config.select_layer != -1:
             raise NotImplementedError('only select_layer == -1 (last hidden state) is implemented')
 
@@ -103,9 +134,8 @@ class InternVLChatModel:
         # 16-row lane-local units for the q/k/v and gate/up GEMVs of the <= 16-row path (r03 kernels; at H = 1536 both help the decode: 1.169 -> 1.12 ms per token,
         # same-box A/B r04; the action expert at K = 768 keeps gate/up on 32-row units): VLASER_DECODE_OPTS=none restores the r03 decode.
         # 'chain' (r05, csrc/chain.hip): q/k/v, gate/up and the down projection on the latency-built kernels (batch <= 8): 1.089 -> 1.038 ms per token, same-box A/B
-        self.llm = QwenStack(sd, 'language_model.', self.config.llm, self.device, skinny=self.use_skinny,
-                             opts=tuple(o for o in os.environ.get('VLASER_DECODE_OPTS', 'qkv16,gu16,chain' if self.config.llm.hidden_size in (768, 1536) else '').split(',')
-                                        if o and o != 'none'))      # (the 16-row units are built for hidden sizes 768 / 1536: 3 / 6 K-steps per wave)
+        # (the 16-row units are built for hidden sizes 768 / 1536: 3 / 6 K-steps per wave: resolve_decode_opts, read at construction)
+        self.llm = QwenStack(sd, 'language_model.', self.config.llm, self.device, skinny=self.use_skinny, opts=self.decode_opts)
         self._alloc_llm()
         return SimpleNamespace(missing_keys=missing, unexpected_keys=unexpected)
 
@@ -293,15 +323,16 @@ class InternVLChatModel:
             eos_token_id = eos_token_id if eos_token_id is not None else getattr(generation_config, 'eos_token_id', None)
         max_new_tokens = max_new_tokens or 20          # HF default max_length heritage
         B = input_ids.shape[0]
-        if B > 16:
-            # the weight-streaming decode takes <= 16 rows per launch: larger batches run as consecutive groups of 16 sequences
+        G = self.decode_group
+        if B > G:
+            # the weight-streaming decode takes <= 16 rows per launch (8 with e4m3 MLP weights at hidden 1536): larger batches run as consecutive groups of G sequences
             if return_logits or visual_features is not None:
-                raise NotImplementedError('return_logits / visual_features are per-group features: call generate() with <= 16 sequences')
+                raise NotImplementedError(f'return_logits / visual_features are per-group features: call generate() with <= {G} sequences')
             tiles = ((input_ids == self.img_context_token_id).sum(1) // self.num_image_token).tolist() if pixel_values is not None else [0] * B
             pad = pad_token_id if pad_token_id is not None else (eos_token_id[0] if isinstance(eos_token_id, (list, tuple)) else eos_token_id) or 0
             outs, off = [], 0
-            for lo in range(0, B, 16):
-                hi = min(B, lo + 16)
+            for lo in range(0, B, G):
+                hi = min(B, lo + G)
                 nt = sum(tiles[lo:hi])
                 outs.append(self.generate(None if pixel_values is None else pixel_values[off:off + nt], input_ids[lo:hi],
                                           None if attention_mask is None else attention_mask[lo:hi], max_new_tokens=max_new_tokens,
@@ -426,11 +457,12 @@ class InternVLChatModel:
         eos_token_id = tokenizer.convert_tokens_to_ids(template.sep.strip())
         generation_config['eos_token_id'] = eos_token_id
         responses = []
-        for b0 in range(0, len(queries), 16):              # the weight-streaming decode handles <= 16 rows per launch
-            n_tiles0, n_tiles1 = sum(num_patches_list[:b0]), sum(num_patches_list[:b0 + 16])
+        G = self.decode_group
+        for b0 in range(0, len(queries), G):               # the weight-streaming decode handles <= 16 rows per launch (8 with e4m3 MLP weights)
+            n_tiles0, n_tiles1 = sum(num_patches_list[:b0]), sum(num_patches_list[:b0 + G])
             pv = None if pixel_values is None else pixel_values[n_tiles0:n_tiles1]
-            out = self.generate(pixel_values=pv, input_ids=model_inputs['input_ids'][b0:b0 + 16],
-                                attention_mask=model_inputs['attention_mask'][b0:b0 + 16], **generation_config)
+            out = self.generate(pixel_values=pv, input_ids=model_inputs['input_ids'][b0:b0 + G],
+                                attention_mask=model_inputs['attention_mask'][b0:b0 + G], **generation_config)
             responses += tokenizer.batch_decode(out, skip_special_tokens=True)
         return [r.split(template.sep.strip())[0].strip() for r in responses]
 

@@ -387,7 +387,7 @@ def pack_down4(W, nw=DOWN4_WAVES, nl=DOWN4_LOADS):
     return v.permute(0, 3, 4, 1, 5, 2, 6).contiguous().reshape(-1)         # [wg, w, l, c, b, i, e]
 
 
-# ---- one-byte MLP weights of the action expert (option 'mlp8'; csrc/chain.hip W8 forms): OCP e4m3 codes + one power-of-two fp32 scale per weight row
+# ---- one-byte MLP weights of the action expert and of the Vlaser-2B LLM's decode (option 'mlp8'; csrc/chain.hip W8 forms): OCP e4m3 codes + one power-of-two fp32 scale per weight row
 E4M3_MAX = 448.0
 GU8_WAVE_BYTES = 64 * 16 + 64 * 8          # a wave's share of a 16-row unit at K = 768: the lanes' K-steps 0 and 1 (16 bytes each), then K-step 2 (8 bytes each)
 
@@ -424,25 +424,34 @@ def pack_gate_up8_e4m3(gate_codes, gate_scale, up_codes, up_scale):
     """e4m3 gate / up codes [I, 768] + row scales -> PackedW (tpu = 1, .scale = fp32 [2I] in packed row order) for vlaser_chain_gu_w8.  Rows as pack_gate_up8; lane
     (r = l & 15, g = l >> 4) of wave w, unit u receives the same 3 x 8 elements W[16u + r, 96w + 32s + 8g : + 8], s = 0, 1, 2 as from pack_skinny(..., 1, 1), in 24 bytes:
     K = 768 gives a wave an ODD number of K-steps, so a unit's share of a wave is 64 x 16 bytes (K-steps 0 and 1 of each lane: one 16-byte load) followed by 64 x 8 bytes
-    (K-step 2: one 8-byte load) -- 1536 contiguous bytes, two requests per unit where the bf16 form issues three."""
+    (K-step 2: one 8-byte load) -- 1536 contiguous bytes, two requests per unit where the bf16 form issues three.
+    K = 1536 (vlaser_chain_gu_w8_k1536, the Vlaser-2B LLM): 6 K-steps W[16u + r, 192w + 32s + 8g : + 8] in 48 bytes per lane = three 16-byte loads, load j the K-steps
+    2j and 2j + 1: a unit's share of a wave is [j = 0..2][lane][16 bytes] = 3072 contiguous bytes, no tail."""
     rows = pack_gate_up8(gate_codes, up_codes)
     N, K = rows.shape
-    assert rows.dtype == torch.uint8 and K == 3 * 32 * SK_WAVES and N % 16 == 0, (rows.dtype, N, K)
+    assert rows.dtype == torch.uint8 and K in (3 * 32 * SK_WAVES, 6 * 32 * SK_WAVES) and N % 16 == 0, (rows.dtype, N, K)
+    scale = pack_gate_up8(gate_scale.reshape(-1, 1), up_scale.reshape(-1, 1)).reshape(-1).to(torch.float32)
+    if K == 6 * 32 * SK_WAVES:
+        v = rows.view(N // 16, 16, SK_WAVES, 3, 2, 4, 8)                        # [u, r, w, j, s2, g, e]
+        return PackedW(v.permute(0, 2, 3, 5, 1, 4, 6).reshape(-1).contiguous(), N, N, K, 1, 1, scale=scale.contiguous())      # [u, w, j, g, r, s2, e]
     v = rows.view(N // 16, 16, SK_WAVES, 3, 4, 8)                               # [u, r, w, s, g, e]
     a = v[:, :, :, :2].permute(0, 2, 4, 1, 3, 5).reshape(N // 16, SK_WAVES, 1024)     # [u, w, g, r, s, e]
     b = v[:, :, :, 2].permute(0, 2, 3, 1, 4).reshape(N // 16, SK_WAVES, 512)          # [u, w, g, r, e]
-    scale = pack_gate_up8(gate_scale.reshape(-1, 1), up_scale.reshape(-1, 1)).reshape(-1).to(torch.float32)
     return PackedW(torch.cat([a, b], dim=2).reshape(-1).contiguous(), N, N, K, 1, 1, scale=scale.contiguous())
 
 
 def unpack_gate_up8_e4m3(W: PackedW):
     """Inverse of pack_gate_up8_e4m3 -> (gate_codes, gate_scale, up_codes, up_scale)."""
     U = W.N // 16
+    gs, us = unpack_gate_up8(W.scale.reshape(-1, 1))
+    if W.K == 6 * 32 * SK_WAVES:
+        v = W.t.view(U, SK_WAVES, 3, 4, 16, 2, 8).permute(0, 4, 1, 2, 5, 3, 6)          # [u, w, j, g, r, s2, e] -> [u, r, w, j, s2, g, e]
+        gc, uc = unpack_gate_up8(v.reshape(W.N, W.K))
+        return gc, gs.reshape(-1), uc, us.reshape(-1)
     t = W.t.view(U, SK_WAVES, GU8_WAVE_BYTES)
     a = t[:, :, :1024].reshape(U, SK_WAVES, 4, 16, 2, 8).permute(0, 3, 1, 4, 2, 5)      # [u, w, g, r, s, e] -> [u, r, w, s, g, e]
     b = t[:, :, 1024:].reshape(U, SK_WAVES, 4, 16, 1, 8).permute(0, 3, 1, 4, 2, 5)
     gc, uc = unpack_gate_up8(torch.cat([a, b], dim=3).reshape(W.N, W.K))
-    gs, us = unpack_gate_up8(W.scale.reshape(-1, 1))
     return gc, gs.reshape(-1), uc, us.reshape(-1)
 
 
@@ -479,12 +488,20 @@ def chain_gu_w8_supported(M, N, K, n_partials, tpu=1):
     return bool(L.lib().vlaser_chain_gu_w8_supported(M, N, K, n_partials, tpu))
 
 
+def chain_gu_w8_k1536_supported(M, N, K, n_partials, tpu=1):
+    return bool(L.lib().vlaser_chain_gu_w8_k1536_supported(M, N, K, n_partials, tpu))
+
+
 def chain_down_w8_supported(M, N, K):
     return bool(L.lib().vlaser_chain_down_w8_supported(M, N, K))
 
 
 def launch_chain_gu_w8(a, stream=None):
     L.check(L.lib().vlaser_chain_gu_w8(C.byref(a), _stream() if stream is None else stream), 'vlaser_chain_gu_w8')
+
+
+def launch_chain_gu_w8_k1536(a, stream=None):
+    L.check(L.lib().vlaser_chain_gu_w8_k1536(C.byref(a), _stream() if stream is None else stream), 'vlaser_chain_gu_w8_k1536')
 
 
 def chain_down_w8(x, W8, scale4, res, h_out, M, N, K, dbg=None, stream=None):
