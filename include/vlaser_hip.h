@@ -291,18 +291,27 @@ int vlaser_chain_gu_w8_k1536(const VlaserSkinnyArgs* args, vl_stream_t stream);
  *   vlaser_reduce_norm_cohost  : C = 1536 RMS, 3 slabs + VL_GUEST_CHAIN_OPROJ,                               128x256 SWIGLU (gate/up) + VL_GUEST_CHAIN_GU
  *                                C = 1536 RMS, 7 slabs + VL_GUEST_CHAIN_DOWN                          64x64 QKV_ROPE (q/k/v, 192 tiles) + VL_GUEST_CHAIN_DOWN
  * (the q/k/v GEMM runs its guest in the looped form, four of vlaser_chain_down's workgroups to one: its 64 idle CUs take one workgroup each.)
+ * An expert with e4m3 MLP weights ('mlp8') rides in the same three hosts with the W8 kinds, the bodies of vlaser_chain_gu_w8 / vlaser_chain_down_w8:
+ *   vlaser_gemm_cohost         : 128x256 SWIGLU (gate/up) + VL_GUEST_CHAIN_GU_W8,     64x64 QKV_ROPE (q/k/v, 192 tiles) + VL_GUEST_CHAIN_DOWN_W8 (looped form)
+ *   vlaser_reduce_norm_cohost  : C = 1536 RMS, 7 slabs + VL_GUEST_CHAIN_DOWN_W8
  * guest == NULL or kind VL_GUEST_NONE: the host alone. */
-enum { VL_GUEST_NONE = 0, VL_GUEST_CHAIN_QKV = 1, VL_GUEST_CHAIN_ATTN = 2, VL_GUEST_CHAIN_OPROJ = 3, VL_GUEST_CHAIN_GU = 4, VL_GUEST_CHAIN_DOWN = 5 };
+enum { VL_GUEST_NONE = 0, VL_GUEST_CHAIN_QKV = 1, VL_GUEST_CHAIN_ATTN = 2, VL_GUEST_CHAIN_OPROJ = 3, VL_GUEST_CHAIN_GU = 4, VL_GUEST_CHAIN_DOWN = 5,
+       VL_GUEST_CHAIN_GU_W8 = 6, VL_GUEST_CHAIN_DOWN_W8 = 7 };
 typedef struct VlaserCohostGuest {
   int kind;              /* VL_GUEST_* */
-  const void* args;      /* the guest's existing argument struct: VlaserSkinnyArgs (QKV, OPROJ, GU), VlaserAttnArgs (ATTN), VlaserChainDownArgs (DOWN) */
+  const void* args;      /* the guest's existing argument struct: VlaserSkinnyArgs (QKV, OPROJ, GU, GU_W8: with w_scale), VlaserAttnArgs (ATTN), VlaserChainDownArgs (DOWN), VlaserChainDownW8Args (DOWN_W8) */
 } VlaserCohostGuest;
 typedef struct VlaserChainDownArgs {      /* vlaser_chain_down's arguments */
   const void* x; int ldx; const void* W; const void* res; void* h_out; int M, N, K; unsigned long long* dbg;
 } VlaserChainDownArgs;
+typedef struct VlaserChainDownW8Args {    /* vlaser_chain_down_w8's arguments: VlaserChainDownArgs' fields, then the packed scales (ops.pack_down4_scales) */
+  const void* x; int ldx; const void* W; const void* res; void* h_out; int M, N, K; unsigned long long* dbg; const float* w_scale;
+} VlaserChainDownW8Args;
 int vlaser_cohost_fused_count(void);            /* launches so far that carried their guest in their own grid (the fallback returns the same 0: this tells them apart) */
 int vlaser_cohost_lab(int mode);                /* timing tools only: 1 = fused kernels run with zero guest workgroups and the guest is skipped (host-alone check); returns the previous mode */
 int vlaser_chain_down_looped(const void* x, int ldx, const void* W, const void* res, void* h_out, int M, int N, int K, vl_stream_t stream);      /* the looped form on its own (tests, tools): vlaser_chain_down's bits */
+/* the looped W8 form on its own: vlaser_chain_down_w8's bits; the shapes of vlaser_chain_down_looped, and a null or misaligned w_scale is refused before any launch */
+int vlaser_chain_down_looped_w8(const void* x, int ldx, const void* W, const float* w_scale, const void* res, void* h_out, int M, int N, int K, vl_stream_t stream);
 int vlaser_gemm_cohost(int epi, const VlaserGemmArgs* args, const VlaserCohostGuest* guest, vl_stream_t stream);
 int vlaser_attn_prefill_cohost(const VlaserAttnArgs* args, const VlaserCohostGuest* guest, vl_stream_t stream);
 int vlaser_reduce_norm_cohost(const void* h_in, const float* partials, int n_partials, const void* bias, const void* ls, int norm_kind, const void* norm_w, const void* norm_b,

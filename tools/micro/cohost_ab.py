@@ -5,10 +5,13 @@ variants in turn.
     python tools/micro/cohost_ab.py                      # off, all five, each pair alone, each pair left out
     python tools/micro/cohost_ab.py off qkv+attn all     # named sets
     python tools/micro/cohost_ab.py lag                  # the lagged pair: off, the four default pairs, those + down_next, down_next alone, all, off
+    python tools/micro/cohost_ab.py mlp8                 # an 'mlp8' model (e4m3 expert MLP weights, W8 guests): off, each default pair alone, the default set, the set minus each pair, off
+    python tools/micro/cohost_ab.py mlp8 off gu all      # named sets on an 'mlp8' model
 
 `down_next` in a set = the down projection rides in the next layer's q/k/v GEMM (pizero.COHOST_LAGGED); `all` = the five pairs of COHOST_PAIRS.
 
-Prints median / min ms per chunk and, against `off` and against `all`, the difference of the medians with the spread of `off` over its rounds."""
+Prints median / min ms per chunk and, against `off` and against `all` (under `mlp8` without named sets: against the default set), the difference of the medians with
+the spread of `off` over its rounds."""
 import os
 import sys
 import time
@@ -24,7 +27,15 @@ def main():
     from vlaser_amd import config as C, synth
     from vlaser_amd.pizero import COHOST_PAIRS, LAG_TOKENS, PiZeroInference
     names = list(COHOST_PAIRS)
-    variants = sys.argv[1:] or (['off', 'all'] + names + ['+'.join(x for x in names if x != n) for n in names] + ['off'])
+    argv = sys.argv[1:]
+    mlp8 = argv[:1] == ['mlp8']
+    argv = argv[1:] if mlp8 else argv
+    ref_set = 'all'
+    if mlp8 and not argv:          # the per-pair rule on the DEFAULT set: alone against off, left out against the set
+        default = next(o for o in PiZeroInference.EULER_DEFAULT.split(',') if o.startswith('cohost='))[len('cohost='):].split('+')
+        ref_set = '+'.join(default)
+        argv = ['off'] + default + [ref_set] + ['+'.join(x for x in default if x != n) for n in default] + ['off']
+    variants = argv or (['off', 'all'] + names + ['+'.join(x for x in names if x != n) for n in names] + ['off'])
     if variants == ['lag']:
         variants = ['off', 'qkv+attn+o+gu', 'qkv+attn+o+gu+down_next', 'down_next', 'all', 'off']
     toks = [() if v == 'off' else tuple(names) if v == 'all' else tuple(v.split('+')) for v in variants]
@@ -39,8 +50,9 @@ def main():
     ids, pv, proprio, noise = bench.make_inputs(vla.base, 1, seed=0)
     ids_d, pv_d, pro_d, noise_d = ids.to(dev), pv.to(dev).to(torch.bfloat16), proprio.to(dev), noise.to(dev)
     valid = (ids != vla.base.pad_token_id).sum(-1).to(dev)
-    m = PiZeroInference(vla, device=dev, max_batch=1, euler_opts='qkv16,gu16,glue1,chain,cohost')
+    m = PiZeroInference(vla, device=dev, max_batch=1, euler_opts='qkv16,gu16,glue1,chain,cohost' + (',mlp8' if mlp8 else ''))
     m.load_state_dict(sd)
+    assert m._cohost_ok(1) and m.expert_mlp_weights == ('fp8' if mlp8 else 'bf16')
     call = lambda: m.infer_action(ids_d, pv_d, proprios=pro_d, noise=noise_d, valid_len=valid)
     graphs, ref = [], None
     for v, s in zip(variants, sets):
@@ -66,9 +78,9 @@ def main():
     off = [ts for v, ts in zip(variants, times) if v == 'off']
     spread = max(max(ts) - min(ts) for ts in off) if off else float('nan')
     m_off = med(off[0]) if off else float('nan')
-    m_all = next((med(ts) for v, ts in zip(variants, times) if v == 'all'), float('nan'))
-    print(f'one model instance, {rounds} rounds x {n} chunks per variant; spread of `off` over its rounds {spread:.3f} ms; all chunks bit-identical\n')
-    print('| pairs on | median ms/chunk | min | max | - off | - all |')
+    m_all = next((med(ts) for v, ts in zip(variants, times) if v == ref_set), float('nan'))
+    print(f'{"mlp8 (e4m3 expert MLP weights), " if mlp8 else ""}one model instance, {rounds} rounds x {n} chunks per variant; spread of `off` over its rounds {spread:.3f} ms; all chunks bit-identical\n')
+    print(f'| pairs on | median ms/chunk | min | max | - off | - {"all" if ref_set == "all" else "`" + ref_set + "`"} |')
     print('|---|---|---|---|---|---|')
     for v, ts in zip(variants, times):
         print(f'| `{v}` | {med(ts):.3f} | {min(ts):.3f} | {max(ts):.3f} | {med(ts) - m_off:+.3f} | {med(ts) - m_all:+.3f} |')

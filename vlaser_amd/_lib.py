@@ -46,6 +46,10 @@ class ChainDownArgs(C.Structure):
     _fields_ = [('x', vp), ('ldx', i32), ('W', vp), ('res', vp), ('h_out', vp), ('M', i32), ('N', i32), ('K', i32), ('dbg', vp)]
 
 
+class ChainDownW8Args(C.Structure):
+    _fields_ = [('x', vp), ('ldx', i32), ('W', vp), ('res', vp), ('h_out', vp), ('M', i32), ('N', i32), ('K', i32), ('dbg', vp), ('w_scale', vp)]
+
+
 class VlaStageArgs(C.Structure):
     _fields_ = [('ids', vp), ('ids_out', vp), ('B', i32), ('T', i32), ('pad_id', i64), ('valid_in', vp), ('valid_is_i64', i32), ('valid_out', vp),
                 ('proprio', vp), ('proprio_out', vp), ('n_proprio', i32), ('noise', vp), ('noise_out', vp), ('n_noise', i32),
@@ -59,7 +63,7 @@ class VlaStageArgs(C.Structure):
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_LS_RES, EPI_RES, EPI_SWIGLU, EPI_QKV_ROPE, EPI_VIT_QKV, EPI_F32, EPI_PARTIAL, EPI_SWIGLU_BWD = range(11)
 ATTN_FULL, ATTN_CAUSAL, ATTN_PREFIX, ATTN_DENSE = range(4)
 PRO_PLAIN, PRO_NORM, PRO_ATTN = range(3)
-GUEST_NONE, GUEST_CHAIN_QKV, GUEST_CHAIN_ATTN, GUEST_CHAIN_OPROJ, GUEST_CHAIN_GU, GUEST_CHAIN_DOWN = range(6)
+GUEST_NONE, GUEST_CHAIN_QKV, GUEST_CHAIN_ATTN, GUEST_CHAIN_OPROJ, GUEST_CHAIN_GU, GUEST_CHAIN_DOWN, GUEST_CHAIN_GU_W8, GUEST_CHAIN_DOWN_W8 = range(8)
 SK_PARTIAL, SK_QKV_ROPE, SK_SWIGLU, SK_F32, SK_BIAS, SK_BIAS_SILU = range(6)
 
 _SIGS = {
@@ -92,6 +96,7 @@ _SIGS = {
     'vlaser_chain_gu': [C.POINTER(SkinnyArgs), vp],
     'vlaser_chain_down': [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp],
     'vlaser_chain_down_looped': [vp, i32, vp, vp, vp, i32, i32, i32, vp],
+    'vlaser_chain_down_looped_w8': [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp],
     'vlaser_chain_gu_w8_supported': [i32, i32, i32, i32, i32],
     'vlaser_chain_gu_w8': [C.POINTER(SkinnyArgs), vp],
     'vlaser_chain_gu_w8_k1536_supported': [i32, i32, i32, i32, i32],

@@ -290,13 +290,13 @@ extern "C" int vlaser_chain_oproj(const VlaserSkinnyArgs* a, vl_stream_t s) {
 
 // ------------------------------------------------------------------------------------------------------------------ co-hosted launches: the guest side on the host
 // (include/vlaser_hip.h, VlaserCohostGuest).  vl_cohost_chain_*: 1 when the guest is that launch AT THE SHAPE ITS FUSED INSTANTIATION IS BUILT FOR (Euler step 0 of a
-// batch-1 chunk: 5 rows, bf16 weights, no timeline stamps) and its arguments pass the stand-alone entry's checks -- then the parameters and the geometry are filled in;
+// batch-1 chunk: 5 rows, no timeline stamps; bf16 weights, or for the *_W8 kinds the e4m3 codes and scales of the stand-alone W8 entries) and its arguments pass the stand-alone entry's checks -- then the parameters and the geometry are filled in;
 // 0 otherwise: the caller launches host, then guest (vl_cohost_guest_launch, which reports a bad argument exactly as the stand-alone entry would).
-VL_INTERNAL int vl_cohost_chain_gu(const VlaserCohostGuest* g, ChainGuP* p, int* wgs, int* lds) {
-  if (!g || g->kind != VL_GUEST_CHAIN_GU || !g->args) return 0;
+VL_INTERNAL int vl_cohost_chain_gu(const VlaserCohostGuest* g, int kind, ChainGuP* p, int* wgs, int* lds) {
+  if (!g || g->kind != kind || (kind != VL_GUEST_CHAIN_GU && kind != VL_GUEST_CHAIN_GU_W8) || !g->args) return 0;
   const VlaserSkinnyArgs* a = (const VlaserSkinnyArgs*)g->args;
   ChainGuGeom q;
-  if (a->dbg || chain_gu_prepare(a, CG_BF16, *p, q)) return 0;
+  if (a->dbg || chain_gu_prepare(a, kind == VL_GUEST_CHAIN_GU_W8 ? CG_W8 : CG_BF16, *p, q)) return 0;
   if (!(q.ns == 3 && q.longest == 5 && a->n_partials == 3 && q.cpt == 1 && q.tpu == 1)) return 0;
   *wgs = q.gx; *lds = q.lds;
   return 1;
@@ -325,18 +325,29 @@ VL_INTERNAL int vl_cohost_chain_oproj(const VlaserCohostGuest* g, ChainOprojP* p
   *wgs = (a->N / 16) * a->k_splits;
   return 1;
 }
-VL_INTERNAL int vl_cohost_chain_down(const VlaserCohostGuest* g, ChainDownP* p, int* wgs) {
-  if (!g || g->kind != VL_GUEST_CHAIN_DOWN || !g->args) return 0;
-  const VlaserChainDownArgs* a = (const VlaserChainDownArgs*)g->args;
-  if (a->dbg || chain_down_prepare(a->x, a->ldx, a->W, nullptr, a->res, a->h_out, a->M, a->N, a->K, nullptr, false, *p)) return 0;
+VL_INTERNAL int vl_cohost_chain_down(const VlaserCohostGuest* g, int kind, ChainDownP* p, int* wgs) {
+  if (!g || g->kind != kind || !g->args) return 0;
+  int M, N;
+  if (kind == VL_GUEST_CHAIN_DOWN_W8) {
+    const VlaserChainDownW8Args* a = (const VlaserChainDownW8Args*)g->args;
+    if (a->dbg || chain_down_prepare(a->x, a->ldx, a->W, a->w_scale, a->res, a->h_out, a->M, a->N, a->K, nullptr, true, *p)) return 0;
+    M = a->M; N = a->N;
+  } else if (kind == VL_GUEST_CHAIN_DOWN) {
+    const VlaserChainDownArgs* a = (const VlaserChainDownArgs*)g->args;
+    if (a->dbg || chain_down_prepare(a->x, a->ldx, a->W, nullptr, a->res, a->h_out, a->M, a->N, a->K, nullptr, false, *p)) return 0;
+    M = a->M; N = a->N;
+  } else {
+    return 0;
+  }
   int cols, groups;
-  *wgs = vlaser_chain_down_geometry(a->N, &cols, &groups);
-  return (a->M + 3) / 4 == 2 && cols == 3 && groups == 1;
+  *wgs = vlaser_chain_down_geometry(N, &cols, &groups);
+  return (M + 3) / 4 == 2 && cols == 3 && groups == 1;
 }
 // the looped form (chain_down_loop_kernel / GuestChainDown4): the same shape, and a workgroup count that four divides; *wgs = workgroups of four units
-VL_INTERNAL int vl_cohost_chain_down4(const VlaserCohostGuest* g, ChainDownP* p, int* wgs) {
+VL_INTERNAL int vl_cohost_chain_down4(const VlaserCohostGuest* g, int kind, ChainDownP* p, int* wgs) {
+  static_assert(GuestChainDown4W8::UNITS == GuestChainDown4::UNITS, "one looped geometry for both weight formats");
   int units;
-  if (!vl_cohost_chain_down(g, p, &units) || units % GuestChainDown4::UNITS) return 0;
+  if (!vl_cohost_chain_down(g, kind, p, &units) || units % GuestChainDown4::UNITS) return 0;
   *wgs = units / GuestChainDown4::UNITS;
   return 1;
 }
@@ -347,12 +358,27 @@ extern "C" int vlaser_chain_down_looped(const void* x, int ldx, const void* W, c
   const VlaserCohostGuest g = {VL_GUEST_CHAIN_DOWN, &a};
   ChainDownP p;
   int wgs;
-  if (!vl_cohost_chain_down4(&g, &p, &wgs)) {
+  if (!vl_cohost_chain_down4(&g, VL_GUEST_CHAIN_DOWN, &p, &wgs)) {
     if (chain_down_prepare(x, ldx, W, nullptr, res, h_out, M, N, K, nullptr, false, p)) return -1;      // (its message)
     vlaser_set_error("vlaser_chain_down_looped: built for 5..8 rows, 3-column units, a workgroup count that 4 divides (got M %d N %d)", M, N);
     return -1;
   }
   hipLaunchKernelGGL((chain_down_loop_kernel<7, 10, 2, 3, 1, GuestChainDown4::UNITS>), dim3(wgs), dim3(7 * 64), 0, (hipStream_t)s, p);
+  VL_LAUNCH_CHECK();
+  return 0;
+}
+/* the same for vlaser_chain_down_w8 (W = ops.pack_down4_e4m3, w_scale = ops.pack_down4_scales): the looped W8 kernel on its own, vlaser_chain_down_w8's bits */
+extern "C" int vlaser_chain_down_looped_w8(const void* x, int ldx, const void* W, const float* w_scale, const void* res, void* h_out, int M, int N, int K, vl_stream_t s) {
+  VlaserChainDownW8Args a = {x, ldx, W, res, h_out, M, N, K, nullptr, w_scale};
+  const VlaserCohostGuest g = {VL_GUEST_CHAIN_DOWN_W8, &a};
+  ChainDownP p;
+  int wgs;
+  if (!vl_cohost_chain_down4(&g, VL_GUEST_CHAIN_DOWN_W8, &p, &wgs)) {
+    if (chain_down_prepare(x, ldx, W, w_scale, res, h_out, M, N, K, nullptr, true, p)) return -1;      // (its message: null or misaligned scales among them)
+    vlaser_set_error("vlaser_chain_down_looped_w8: built for 5..8 rows, 3-column units, a workgroup count that 4 divides (got M %d N %d)", M, N);
+    return -1;
+  }
+  hipLaunchKernelGGL((chain_down_loop_kernel<7, 10, 2, 3, 1, GuestChainDown4W8::UNITS, true>), dim3(wgs), dim3(7 * 64), 0, (hipStream_t)s, p);
   VL_LAUNCH_CHECK();
   return 0;
 }
@@ -367,6 +393,11 @@ VL_INTERNAL int vl_cohost_guest_launch(const VlaserCohostGuest* g, vl_stream_t s
     case VL_GUEST_CHAIN_DOWN: {
       const VlaserChainDownArgs* a = (const VlaserChainDownArgs*)g->args;
       return vlaser_chain_down(a->x, a->ldx, a->W, a->res, a->h_out, a->M, a->N, a->K, a->dbg, s);
+    }
+    case VL_GUEST_CHAIN_GU_W8: return vlaser_chain_gu_w8((const VlaserSkinnyArgs*)g->args, s);
+    case VL_GUEST_CHAIN_DOWN_W8: {
+      const VlaserChainDownW8Args* a = (const VlaserChainDownW8Args*)g->args;
+      return vlaser_chain_down_w8(a->x, a->ldx, a->W, a->w_scale, a->res, a->h_out, a->M, a->N, a->K, a->dbg, s);
     }
     default: break;
   }

@@ -162,15 +162,15 @@ __global__ __launch_bounds__(NW * 64) void chain_down_kernel(ChainDownP p) {
 // The looped form (chain_down_loop.inc): workgroup wg does the work of the stand-alone launch's workgroups wg * UNITS .. + UNITS - 1 -- the activation slices, which
 // every one of those reads alike, requested once, the weights of unit u + 1 in flight under unit u's MFMAs.  Built for a launch that has few CUs to itself: the guest of
 // the joint prefill's q/k/v GEMM (GuestChainDown4 below: 64 idle CUs, one workgroup each because the fused launch carries the host's 128 KB LDS request; four rounds of
-// the stand-alone geometry there would outlast the host).  Bit-identical to chain_down_kernel; bf16 weights, CG = 1.
-template <int NW, int NL, int RG, int COLS, int CG, int UNITS>
+// the stand-alone geometry there would outlast the host).  Bit-identical to chain_down_kernel in the same weight format (W8: the e4m3 codes of ops.pack_down4_e4m3, half the requests per unit); CG = 1.
+template <int NW, int NL, int RG, int COLS, int CG, int UNITS, bool W8 = false>
 __device__ __forceinline__ void chain_down_loop_body(const ChainDownP& p, const int wg) {
 #define VL_WG_X wg
 #include "chain_down_loop.inc"
 #undef VL_WG_X
 }
-template <int NW, int NL, int RG, int COLS, int CG, int UNITS>
-__global__ __launch_bounds__(NW * 64) void chain_down_loop_kernel(ChainDownP p) {      // the looped body on its own (vlaser_chain_down_looped: tests, tools)
+template <int NW, int NL, int RG, int COLS, int CG, int UNITS, bool W8 = false>
+__global__ __launch_bounds__(NW * 64) void chain_down_loop_kernel(ChainDownP p) {      // the looped body on its own (vlaser_chain_down_looped / _looped_w8: tests, tools)
 #define VL_WG_X blockIdx.x
 #include "chain_down_loop.inc"
 #undef VL_WG_X
@@ -276,6 +276,11 @@ struct GuestChainGu {
   static constexpr int THREADS = 512;
   static __device__ __forceinline__ void run(const P& p, int gwg) { chain_gu_body<3, 5, 3, 1, 1, false>(p, gwg); }
 };
+struct GuestChainGuW8 {          // the e4m3 forms (an 'mlp8' expert): the stand-alone W8 kernels' bodies at the same shapes
+  typedef ChainGuP P;
+  static constexpr int THREADS = 512;
+  static __device__ __forceinline__ void run(const P& p, int gwg) { chain_gu_body<3, 5, 3, 1, 1, false, true>(p, gwg); }
+};
 struct GuestChainOproj {
   typedef ChainOprojP P;
   static constexpr int THREADS = 512;
@@ -296,6 +301,19 @@ struct GuestChainDown4 {
   static __device__ __forceinline__ void run(const P& p, int gwg) {
     if ((gwg + 1) * (UNITS * 3) > p.N) return;          // (a grid rounded up past the guest's workgroups)
     chain_down_loop_body<7, 10, 2, 3, 1, UNITS>(p, gwg);
+  }
+};
+struct GuestChainDownW8 {
+  typedef ChainDownP P;
+  static constexpr int THREADS = 7 * 64;
+  static __device__ __forceinline__ void run(const P& p, int gwg) { chain_down_body<7, 10, 2, 3, 1, false, true>(p, gwg); }
+};
+struct GuestChainDown4W8 {
+  typedef ChainDownP P;
+  static constexpr int THREADS = 7 * 64, UNITS = 4;
+  static __device__ __forceinline__ void run(const P& p, int gwg) {
+    if ((gwg + 1) * (UNITS * 3) > p.N) return;          // (a grid rounded up past the guest's workgroups)
+    chain_down_loop_body<7, 10, 2, 3, 1, UNITS, true>(p, gwg);
   }
 };
 // one-wave bodies: ONE wave per guest workgroup, the stand-alone launch's geometry (the host's other waves return at once).  Several to a workgroup were measured and
@@ -321,12 +339,13 @@ struct GuestChainQkv {
 
 // host side (csrc/chain.hip); internal to the library: hidden, not part of the C ABI
 #define VL_INTERNAL __attribute__((visibility("hidden")))
-VL_INTERNAL int vl_cohost_chain_gu(const VlaserCohostGuest* g, ChainGuP* p, int* wgs, int* lds);
+// (the gate/up and down preparations take the guest kind they are asked for: the bf16 kinds or their e4m3 counterparts VL_GUEST_CHAIN_GU_W8 / _DOWN_W8)
+VL_INTERNAL int vl_cohost_chain_gu(const VlaserCohostGuest* g, int kind, ChainGuP* p, int* wgs, int* lds);
 VL_INTERNAL int vl_cohost_chain_qkv(const VlaserCohostGuest* g, ChainQkvP* p, int* units, int* lds_unit);
 VL_INTERNAL int vl_cohost_chain_attn(const VlaserCohostGuest* g, ChainAttnP* p, int* waves);
 VL_INTERNAL int vl_cohost_chain_oproj(const VlaserCohostGuest* g, ChainOprojP* p, int* wgs, int* lds);
-VL_INTERNAL int vl_cohost_chain_down(const VlaserCohostGuest* g, ChainDownP* p, int* wgs);
-VL_INTERNAL int vl_cohost_chain_down4(const VlaserCohostGuest* g, ChainDownP* p, int* wgs);      // the looped form: *wgs = workgroups of four units
+VL_INTERNAL int vl_cohost_chain_down(const VlaserCohostGuest* g, int kind, ChainDownP* p, int* wgs);
+VL_INTERNAL int vl_cohost_chain_down4(const VlaserCohostGuest* g, int kind, ChainDownP* p, int* wgs);      // the looped form: *wgs = workgroups of four units
 VL_INTERNAL int vl_cohost_guest_launch(const VlaserCohostGuest* g, vl_stream_t s);      // the guest on its own, behind its host: what every pair without a fused instantiation does
 VL_INTERNAL void vl_cohost_count_fused();          // one more launch that carried its guest (vlaser_cohost_fused_count)
 VL_INTERNAL bool vl_cohost_lab_zero_guests();      // vlaser_cohost_lab(1): fused kernels launched with no guest workgroups

@@ -1136,15 +1136,23 @@ static int launch(const VlaserGemmArgs* args, hipStream_t stream, const VlaserCo
     if (guest && hosted && nb == 1) {
       if constexpr (EPI == VL_EPI_QKV_ROPE) {
         ChainDownP gp; int wgs;
-        if (bm == 1564 && blocks(64, 64) <= 192 && vl_cohost_chain_down4(guest, &gp, &wgs)) {
+        if (bm == 1564 && blocks(64, 64) <= 192 && vl_cohost_chain_down4(guest, VL_GUEST_CHAIN_DOWN, &gp, &wgs)) {
           *hosted = 1;
           return launch_glds_cohost<GuestChainDown4, EPI, 64, 64, 2, 2, 8, PIPE>(args, stream, splits, gp, wgs, 0);
         }
+        if (bm == 1564 && blocks(64, 64) <= 192 && vl_cohost_chain_down4(guest, VL_GUEST_CHAIN_DOWN_W8, &gp, &wgs)) {      // an 'mlp8' expert: the looped W8 body
+          *hosted = 1;
+          return launch_glds_cohost<GuestChainDown4W8, EPI, 64, 64, 2, 2, 8, PIPE>(args, stream, splits, gp, wgs, 0);
+        }
       } else if constexpr (EPI == VL_EPI_SWIGLU) {
         ChainGuP gp; int wgs, lds;
-        if (bm == 1200 && vl_cohost_chain_gu(guest, &gp, &wgs, &lds)) {
+        if (bm == 1200 && vl_cohost_chain_gu(guest, VL_GUEST_CHAIN_GU, &gp, &wgs, &lds)) {
           *hosted = 1;
           return launch_glds_cohost<GuestChainGu, EPI, 128, 256, 2, 4, 3, SPREAD>(args, stream, splits, gp, wgs, lds);
+        }
+        if (bm == 1200 && vl_cohost_chain_gu(guest, VL_GUEST_CHAIN_GU_W8, &gp, &wgs, &lds)) {
+          *hosted = 1;
+          return launch_glds_cohost<GuestChainGuW8, EPI, 128, 256, 2, 4, 3, SPREAD>(args, stream, splits, gp, wgs, lds);
         }
       } else {
         ChainAttnP gp; int waves;

@@ -1391,7 +1391,8 @@ extern "C" int vlaser_reduce_norm_cohost(const void* h_in, const float* partials
       if (vl_cohost_chain_oproj(guest, &gp, &wgs, &lds)) return launch_reduce_norm_cohost<GuestChainOproj, 3>(h, gp, wgs, lds, (hipStream_t)s);
     } else {
       ChainDownP gp;
-      if (vl_cohost_chain_down(guest, &gp, &wgs)) return launch_reduce_norm_cohost<GuestChainDown, 7>(h, gp, wgs, 0, (hipStream_t)s);
+      if (vl_cohost_chain_down(guest, VL_GUEST_CHAIN_DOWN, &gp, &wgs)) return launch_reduce_norm_cohost<GuestChainDown, 7>(h, gp, wgs, 0, (hipStream_t)s);
+      if (vl_cohost_chain_down(guest, VL_GUEST_CHAIN_DOWN_W8, &gp, &wgs)) return launch_reduce_norm_cohost<GuestChainDownW8, 7>(h, gp, wgs, 0, (hipStream_t)s);
     }
   }
   if (int rc = vlaser_reduce_norm(h_in, partials, S, bias, ls, norm_kind, nw, nb, eps, h_out, x_out, M, C, s)) return rc;

@@ -448,22 +448,31 @@ def skinny_layer_plan(stack, lw, sb, h_in, partials, n_partials, cache, layer, r
 
 
 _GUEST_KINDS = {'qkv': L.GUEST_CHAIN_QKV, 'attn': L.GUEST_CHAIN_ATTN, 'o': L.GUEST_CHAIN_OPROJ, 'gu': L.GUEST_CHAIN_GU, 'down': L.GUEST_CHAIN_DOWN}
+_GUEST_KINDS_W8 = {'gu': L.GUEST_CHAIN_GU_W8, 'down': L.GUEST_CHAIN_DOWN_W8}      # the MLP launches of an 'mlp8' plan (e4m3 weights); the other three read no MLP weight
 
 
 def plan_guest(plan, name):
-    """Launch `name` of a chain plan (chain and chain_ao, bf16 weights) as the guest descriptor of a co-hosted launch; built once per plan.  It points at the plan's own
-    argument struct, so what skinny_layer_plan brings up to date is what the host's launch reads."""
+    """Launch `name` of a chain plan (chain and chain_ao) as the guest descriptor of a co-hosted launch; built once per plan.  It points at the plan's own
+    argument struct, so what skinny_layer_plan brings up to date is what the host's launch reads.  The gate/up and down launches of an 'mlp8' plan become the W8 kinds:
+    gate/up on the plan's own struct (it carries w_scale), down on a struct of the operands its launch was planned with (the layer's codes and packed scales)."""
     g = plan.guests.get(name)
     if g is None:
         assert plan.chain and plan.chain_ao
         launch, args = next((l, a) for n, l, a in plan.launches if n == name)
-        if name == 'down':
+        kind = _GUEST_KINDS[name]
+        if name == 'down' and launch is _chain_down_w8:
+            sb, lw, M, H, I, _ = args
+            kind, a = _GUEST_KINDS_W8[name], ops.chain_down_w8_args(sb.act, lw.down8, lw.down8_scale, sb.hB, sb.hC, M, H, I)
+        elif name == 'down':
             assert launch is _chain_down
             sb, W4, M, H, I, _ = args
             a = ops.chain_down_args(sb.act, W4, sb.hB, sb.hC, M, H, I)
         else:
+            if name == 'gu' and launch is not ops.launch_chain_gu:
+                assert launch is ops.launch_chain_gu_w8          # (the K = 1536 form belongs to the greedy decode, which has no joint prefill)
+                kind = _GUEST_KINDS_W8[name]
             a = args[0]
-        g = plan.guests[name] = ops.cohost_guest(_GUEST_KINDS[name], a)
+        g = plan.guests[name] = ops.cohost_guest(kind, a)
     return g
 
 

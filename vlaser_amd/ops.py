@@ -131,7 +131,7 @@ def gemm(epi, A, W, out=None, bias=None, res=None, ls=None, N=None, **kw):
 
 
 def cohost_guest(kind, args):
-    """Guest descriptor of a co-hosted launch: kind = L.GUEST_*, args = the guest's own ctypes argument struct (SkinnyArgs / AttnArgs / ChainDownArgs), read when the
+    """Guest descriptor of a co-hosted launch: kind = L.GUEST_*, args = the guest's own ctypes argument struct (SkinnyArgs / AttnArgs / ChainDownArgs / ChainDownW8Args), read when the
     host is launched.  The descriptor keeps the struct alive."""
     g = L.CohostGuest()
     g.kind, g.args = kind, C.addressof(args)
@@ -144,6 +144,15 @@ def chain_down_args(x, W4, res, h_out, M, N, K):
     assert x.dtype == BF16 and res.dtype == BF16 and h_out.dtype == BF16 and x.stride(-1) == 1 and res.data_ptr() != h_out.data_ptr()
     a = L.ChainDownArgs()
     a.x, a.ldx, a.W, a.res, a.h_out, a.M, a.N, a.K = x.data_ptr(), x.stride(0), W4.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K
+    return a
+
+
+def chain_down_w8_args(x, W8, scale4, res, h_out, M, N, K):
+    """vlaser_chain_down_w8's arguments as a struct (the guest of a co-hosted launch of an 'mlp8' expert)."""
+    assert x.dtype == BF16 and res.dtype == BF16 and h_out.dtype == BF16 and x.stride(-1) == 1 and res.data_ptr() != h_out.data_ptr()
+    assert W8.dtype == torch.uint8 and scale4.dtype == torch.float32 and scale4.is_contiguous()
+    a = L.ChainDownW8Args()
+    a.x, a.ldx, a.W, a.res, a.h_out, a.M, a.N, a.K, a.w_scale = x.data_ptr(), x.stride(0), W8.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K, scale4.data_ptr()
     return a
 
 
@@ -565,6 +574,14 @@ def chain_down_looped(x, W4, res, h_out, M, N, K, stream=None):
     assert x.dtype == BF16 and res.dtype == BF16 and h_out.dtype == BF16 and x.stride(-1) == 1 and res.data_ptr() != h_out.data_ptr()
     L.check(L.lib().vlaser_chain_down_looped(x.data_ptr(), x.stride(0), W4.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K, _stream() if stream is None else stream),
             'vlaser_chain_down_looped')
+
+
+def chain_down_looped_w8(x, W8, scale4, res, h_out, M, N, K, stream=None):
+    """chain_down_w8 by the looped W8 kernel (the guest body of the co-hosted q/k/v GEMM under 'mlp8') as a launch of its own; the same bits."""
+    assert x.dtype == BF16 and res.dtype == BF16 and h_out.dtype == BF16 and x.stride(-1) == 1 and res.data_ptr() != h_out.data_ptr()
+    assert W8.dtype == torch.uint8 and scale4.dtype == torch.float32 and scale4.is_contiguous()
+    L.check(L.lib().vlaser_chain_down_looped_w8(x.data_ptr(), x.stride(0), W8.data_ptr(), scale4.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K,
+                                                _stream() if stream is None else stream), 'vlaser_chain_down_looped_w8')
 
 
 # measured on the action-expert chunk: 72 / 100 / 130 / 160 target blocks -> 16.63 / 16.52 / 16.48 / 16.50 ms

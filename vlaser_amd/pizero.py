@@ -112,6 +112,10 @@ def stage_pixels(pixel_values, out, dev):
 # Co-hosted joint prefill ('cohost'): which prefill launch of VLM layer l carries which launch of expert layer l of Euler step 0 (guest -> host, names of
 # engine.prefill_layer_launches / of a chain plan's launches).  The q/k/v GEMM hosts nobody: it writes the prefix K / V^T its own layer's guests read.
 COHOST_PAIRS = {'qkv': 'attn', 'attn': 'o', 'o': 'seam_o', 'gu': 'gu', 'down': 'seam_d'}
+# Pairs of the DEFAULT set that an 'mlp8' model (e4m3 expert MLP weights) leaves un-hosted: under mlp8 the expert's o_proj in the first seam is worth 0.056-0.060 ms in the
+# set, under the spread of the un-hosted schedule in two of three jobs (profiles/cohost_fp8_ab.md; the rule of profiles/cohost_ab.md, alone AND left out of the set).  Only
+# the default is trimmed: an option string that names the pair gets it.
+COHOST_MLP8_DEFAULT_OFF = ('o',)
 
 
 # Lagged pairs (guest -> host launch of the NEXT VLM layer), chosen per call with cohost_plan's `lagged`: the expert's down projection of layer l in the q/k/v GEMM of VLM
@@ -202,7 +206,7 @@ class PiZero:
     #          footprint (1.16 -> 0.58 GB at full depth).  Weight-only: bf16 MFMAs and summation orders unchanged, so the chunk is bit-identical to the default path run
     #          on the dequantised weights.  It is NOT the bf16 model: on the synthetic test model the chunk moves by 1.5e-2 (the reference's own bf16 mode sits 6.5e-3 to
     #          1.6e-2 from its fp32 chunk); the deviation on released checkpoints is unmeasured.  A/B: profiles/fp8_mlp_ab.md.  OFF by default
-    #   cohost (needs chain + qkv16 + gu16 + glue1; batch 1 with the proprio row riding, bf16 expert weights, no general masks -- today's schedule otherwise): the first
+    #   cohost (needs chain + qkv16 + gu16 + glue1; batch 1 with the proprio row riding, no general masks -- today's schedule otherwise; bf16 or 'mlp8' expert weights): the first
     #          pass through the expert (Euler step 0, the five rows that carry the proprio token) is issued INSIDE the joint prefill: expert layer l needs the prefix K / V^T
     #          of VLM layer l and its own previous layer only, so its launches ride as extra workgroups of the prefill's own launches (COHOST_PAIRS; csrc/chain_kernels.h)
     #          on the CUs their single-round grids leave idle.  One queue, no flags, no polling; bit-identical (same bodies, same summation orders).
@@ -213,6 +217,9 @@ class PiZero:
     #          (COHOST_LAGGED; 192 workgroups of one per CU leave 64 CUs idle for 12 us), run there by the looped body -- 64 workgroups of four units, the activations
     #          requested once (csrc/chain_down_loop.inc).  The fused launch lasts 12.75 us against the host's 11.97, and a 6.7 us launch leaves the chain 27 times:
     #          -0.14 ms per chunk in the set, -0.16 ms alone, against a 0.07 ms spread; bench.py 11.087 -> 10.935 ms.  ON.  profiles/cohost_lag_ab.md
+    #          With 'mlp8' the expert's gate/up and down projection ride as the W8 guest kinds (the stand-alone W8 kernels' bodies, the looped W8 body in the q/k/v GEMM):
+    #          bench.py 10.731 -> 10.260 ms with the five pairs named, 0.63 ms under the default model.  expert_mlp_weights='fp8' without an option string hosts the
+    #          default set minus COHOST_MLP8_DEFAULT_OFF.  profiles/cohost_fp8_ab.md
     EULER_DEFAULT = 'qkv16,gu16,glue1,chain,cohost=qkv+attn+o+gu+down_next'      # (gu16 ON with chain since r05: 224 workgroups x 5 units instead of 187 x 3, 11.79 -> 11.68 ms per chunk, same-box A/B)
 
     ERR_BITS = {1: 'image_text_proprio_mask: the keys the proprio row sees are not a contiguous valid prefix',
@@ -260,6 +267,9 @@ class PiZero:
             if missing:
                 raise ValueError(f"Euler option 'mlp8' (expert_mlp_weights='fp8') needs {', '.join(missing)}: the e4m3 MLP weights are read by the chain kernels' 16-row-unit forms only")
         self.expert_mlp_weights = 'fp8' if 'mlp8' in self.euler_opts else 'bf16'
+        if euler_opts is None and 'VLASER_EULER' not in os.environ and self.expert_mlp_weights == 'fp8':      # the default pair set of an mlp8 model
+            self.euler_opts = tuple('cohost=' + '+'.join(x for x in o[len('cohost='):].split('+') if x not in COHOST_MLP8_DEFAULT_OFF) if o.startswith('cohost=') else o
+                                    for o in self.euler_opts)
         # 'cohost' / 'cohost=a+b': the pairs of the co-hosted joint prefill that are switched on (None: the option is off)
         # cohost_lagged: the guests that ride one VLM layer later ('down_next': COHOST_LAGGED)
         self.cohost_pairs, self.cohost_lagged = None, ()
@@ -424,7 +434,7 @@ class PiZero:
 
     def _cohost_ok(self, B):
         """Whether this call takes the co-hosted joint prefill: the option, and the one case its fused launches are built for."""
-        return (self.cohost_pairs is not None and self._glue1 and self._ride(B) and B == 1 and not self.general_masks and self.expert_mlp_weights == 'bf16')
+        return (self.cohost_pairs is not None and self._glue1 and self._ride(B) and B == 1 and not self.general_masks)      # (either weight format: an 'mlp8' expert's gate/up and down ride as the W8 guest kinds)
 
     def _run_joint(self, B):
         """Joint prefill + the first pass through the expert (Euler step 0: proprio row + action rows) as ONE sequence of launches: expert layer l's five launches ride in
