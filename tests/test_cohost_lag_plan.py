@@ -98,6 +98,7 @@ def test_one_layer_has_nothing_to_lag():
 
 
 def test_option_tokens():
-    """'down_next' among the pairs of the Euler option: parsed without a GPU by the same code PiZero.__init__ runs."""
-    from vlaser_amd.pizero import LAG_TOKENS
+    """'down_next' among the pairs of the Euler option: parsed without a GPU by the function PiZero.__init__ calls (pizero.resolve_euler_opts; tests/test_euler_opts.py)."""
+    from vlaser_amd.pizero import LAG_TOKENS, resolve_euler_opts
+    assert resolve_euler_opts('qkv16,gu16,glue1,chain,cohost=qkv+down_next')[2:] == (('qkv',), ('down',))
     assert LAG_TOKENS == {'down_next': 'down'} and all(v in COHOST_LAGGED for v in LAG_TOKENS.values())

@@ -134,11 +134,7 @@ __device__ __forceinline__ void attn_prefill_body(const AttnP& p, const int bx, 
 #define VL_GRID_X gridDim.x
 #define VL_GRID_Y gridDim.y
 #include "attn_prefill.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 
 // ------------------------------------------------------------------------------------------------ skinny
@@ -335,17 +331,9 @@ __global__ __launch_bounds__(256) void attn_skinny_kernel(AttnP p) {
 }
 template <int HD, int KS, int TK, bool TAIL = false, bool HOST = false, bool DENSE = false, bool VARLEN = false>
 __global__ __launch_bounds__(256 * KS) void attn_prefill_kernel(AttnP p) {
-#define VL_WG_X blockIdx.x
-#define VL_WG_Y blockIdx.y
-#define VL_WG_Z blockIdx.z
-#define VL_GRID_X gridDim.x
-#define VL_GRID_Y gridDim.y
+#include "wg_bind.inc"
 #include "attn_prefill.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 
 // Co-hosted launch (csrc/chain_kernels.h): the prefill attention's (query block, head) grid, its x extent lengthened; workgroups bx >= host_gx run guest workgroup

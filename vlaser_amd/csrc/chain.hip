@@ -16,6 +16,7 @@
 //                independent 4 x 4 x 4 blocks per instruction = 4 columns x 4 rows x 64 k), adds the residual and stores the next layer's bf16
 //                residual stream -- the consumer loads 6 KB instead of 66 KB and runs no slab reduction
 
+#include <cstddef>
 #include "chain_kernels.h"
 
 
@@ -289,17 +290,18 @@ extern "C" int vlaser_chain_oproj(const VlaserSkinnyArgs* a, vl_stream_t s) {
 
 
 // ------------------------------------------------------------------------------------------------------------------ co-hosted launches: the guest side on the host
-// (include/vlaser_hip.h, VlaserCohostGuest).  vl_cohost_chain_*: 1 when the guest is that launch AT THE SHAPE ITS FUSED INSTANTIATION IS BUILT FOR (Euler step 0 of a
+// (include/vlaser_hip.h, VlaserCohostGuest).  vl_cohost_chain_*: non-zero (gate/up and down, which take either weight format: 1 = bf16, 2 = e4m3) when the guest is that launch AT THE SHAPE ITS FUSED INSTANTIATION IS BUILT FOR (Euler step 0 of a
 // batch-1 chunk: 5 rows, no timeline stamps; bf16 weights, or for the *_W8 kinds the e4m3 codes and scales of the stand-alone W8 entries) and its arguments pass the stand-alone entry's checks -- then the parameters and the geometry are filled in;
 // 0 otherwise: the caller launches host, then guest (vl_cohost_guest_launch, which reports a bad argument exactly as the stand-alone entry would).
-VL_INTERNAL int vl_cohost_chain_gu(const VlaserCohostGuest* g, int kind, ChainGuP* p, int* wgs, int* lds) {
-  if (!g || g->kind != kind || (kind != VL_GUEST_CHAIN_GU && kind != VL_GUEST_CHAIN_GU_W8) || !g->args) return 0;
+VL_INTERNAL int vl_cohost_chain_gu(const VlaserCohostGuest* g, ChainGuP* p, int* wgs, int* lds) {
+  if (!g || (g->kind != VL_GUEST_CHAIN_GU && g->kind != VL_GUEST_CHAIN_GU_W8) || !g->args) return 0;
+  const bool w8 = g->kind == VL_GUEST_CHAIN_GU_W8;
   const VlaserSkinnyArgs* a = (const VlaserSkinnyArgs*)g->args;
   ChainGuGeom q;
-  if (a->dbg || chain_gu_prepare(a, kind == VL_GUEST_CHAIN_GU_W8 ? CG_W8 : CG_BF16, *p, q)) return 0;
+  if (a->dbg || chain_gu_prepare(a, w8 ? CG_W8 : CG_BF16, *p, q)) return 0;
   if (!(q.ns == 3 && q.longest == 5 && a->n_partials == 3 && q.cpt == 1 && q.tpu == 1)) return 0;
   *wgs = q.gx; *lds = q.lds;
-  return 1;
+  return w8 ? 2 : 1;
 }
 VL_INTERNAL int vl_cohost_chain_qkv(const VlaserCohostGuest* g, ChainQkvP* p, int* units, int* lds_unit) {
   if (!g || g->kind != VL_GUEST_CHAIN_QKV || !g->args) return 0;
@@ -325,62 +327,58 @@ VL_INTERNAL int vl_cohost_chain_oproj(const VlaserCohostGuest* g, ChainOprojP* p
   *wgs = (a->N / 16) * a->k_splits;
   return 1;
 }
-VL_INTERNAL int vl_cohost_chain_down(const VlaserCohostGuest* g, int kind, ChainDownP* p, int* wgs) {
-  if (!g || g->kind != kind || !g->args) return 0;
-  int M, N;
-  if (kind == VL_GUEST_CHAIN_DOWN_W8) {
-    const VlaserChainDownW8Args* a = (const VlaserChainDownW8Args*)g->args;
-    if (a->dbg || chain_down_prepare(a->x, a->ldx, a->W, a->w_scale, a->res, a->h_out, a->M, a->N, a->K, nullptr, true, *p)) return 0;
-    M = a->M; N = a->N;
-  } else if (kind == VL_GUEST_CHAIN_DOWN) {
-    const VlaserChainDownArgs* a = (const VlaserChainDownArgs*)g->args;
-    if (a->dbg || chain_down_prepare(a->x, a->ldx, a->W, nullptr, a->res, a->h_out, a->M, a->N, a->K, nullptr, false, *p)) return 0;
-    M = a->M; N = a->N;
-  } else {
-    return 0;
-  }
+// The two down kinds share one argument prefix (VlaserChainDownW8Args = VlaserChainDownArgs + w_scale): both are read through it, w_scale only where the kind has it.
+#define CD_SHARED(F) static_assert(offsetof(VlaserChainDownW8Args, F) == offsetof(VlaserChainDownArgs, F) && sizeof(VlaserChainDownW8Args::F) == sizeof(VlaserChainDownArgs::F), #F)
+CD_SHARED(x); CD_SHARED(ldx); CD_SHARED(W); CD_SHARED(res); CD_SHARED(h_out); CD_SHARED(M); CD_SHARED(N); CD_SHARED(K); CD_SHARED(dbg);
+#undef CD_SHARED
+static bool chain_down_guest(const VlaserCohostGuest* g, const VlaserChainDownArgs** a, bool* w8, const float** w_scale) {
+  if (!g || (g->kind != VL_GUEST_CHAIN_DOWN && g->kind != VL_GUEST_CHAIN_DOWN_W8) || !g->args) return false;
+  *a = (const VlaserChainDownArgs*)g->args;
+  *w8 = g->kind == VL_GUEST_CHAIN_DOWN_W8;
+  *w_scale = *w8 ? ((const VlaserChainDownW8Args*)g->args)->w_scale : nullptr;
+  return true;
+}
+VL_INTERNAL int vl_cohost_chain_down(const VlaserCohostGuest* g, ChainDownP* p, int* wgs) {
+  const VlaserChainDownArgs* a; bool w8; const float* w_scale;
+  if (!chain_down_guest(g, &a, &w8, &w_scale)) return 0;
+  if (a->dbg || chain_down_prepare(a->x, a->ldx, a->W, w_scale, a->res, a->h_out, a->M, a->N, a->K, nullptr, w8, *p)) return 0;
   int cols, groups;
-  *wgs = vlaser_chain_down_geometry(N, &cols, &groups);
-  return (M + 3) / 4 == 2 && cols == 3 && groups == 1;
+  *wgs = vlaser_chain_down_geometry(a->N, &cols, &groups);
+  if (!((a->M + 3) / 4 == 2 && cols == 3 && groups == 1)) return 0;
+  return w8 ? 2 : 1;
 }
 // the looped form (chain_down_loop_kernel / GuestChainDown4): the same shape, and a workgroup count that four divides; *wgs = workgroups of four units
-VL_INTERNAL int vl_cohost_chain_down4(const VlaserCohostGuest* g, int kind, ChainDownP* p, int* wgs) {
+VL_INTERNAL int vl_cohost_chain_down4(const VlaserCohostGuest* g, ChainDownP* p, int* wgs) {
   static_assert(GuestChainDown4W8::UNITS == GuestChainDown4::UNITS, "one looped geometry for both weight formats");
   int units;
-  if (!vl_cohost_chain_down(g, kind, p, &units) || units % GuestChainDown4::UNITS) return 0;
+  const int fmt = vl_cohost_chain_down(g, p, &units);
+  if (!fmt || units % GuestChainDown4::UNITS) return 0;
   *wgs = units / GuestChainDown4::UNITS;
-  return 1;
+  return fmt;
 }
-/* vlaser_chain_down at the shape the looped form is built for (M in 5..8, cols 3, one group, workgroups a multiple of 4, bf16 weights), run by the looped kernel on its
-   own: a quarter of the workgroups, four units each -- what the guest workgroups of the co-hosted q/k/v GEMM run.  Bit-identical to vlaser_chain_down.  Tests and tools. */
+/* vlaser_chain_down / _w8 at the shape the looped form is built for (M in 5..8, cols 3, one group, workgroups a multiple of 4), run by the looped kernel of the weight format
+   on its own: a quarter of the workgroups, four units each -- what the guest workgroups of the co-hosted q/k/v GEMM run.  Bit-identical to the stand-alone entry of the same
+   format (W8: W = ops.pack_down4_e4m3, w_scale = ops.pack_down4_scales).  Tests and tools. */
+template <bool W8>
+static int chain_down_looped(const void* x, int ldx, const void* W, const float* w_scale, const void* res, void* h_out, int M, int N, int K, vl_stream_t s) {
+  const VlaserChainDownW8Args a = {x, ldx, W, res, h_out, M, N, K, nullptr, w_scale};
+  const VlaserCohostGuest g = {W8 ? VL_GUEST_CHAIN_DOWN_W8 : VL_GUEST_CHAIN_DOWN, &a};
+  ChainDownP p;
+  int wgs;
+  if (!vl_cohost_chain_down4(&g, &p, &wgs)) {
+    if (chain_down_prepare(x, ldx, W, w_scale, res, h_out, M, N, K, nullptr, W8, p)) return -1;      // (its message: W8, null or misaligned scales among them)
+    vlaser_set_error("vlaser_chain_down_looped%s: built for 5..8 rows, 3-column units, a workgroup count that 4 divides (got M %d N %d)", W8 ? "_w8" : "", M, N);
+    return -1;
+  }
+  hipLaunchKernelGGL((chain_down_loop_kernel<7, 10, 2, 3, 1, GuestChainDown4::UNITS, W8>), dim3(wgs), dim3(7 * 64), 0, (hipStream_t)s, p);
+  VL_LAUNCH_CHECK();
+  return 0;
+}
 extern "C" int vlaser_chain_down_looped(const void* x, int ldx, const void* W, const void* res, void* h_out, int M, int N, int K, vl_stream_t s) {
-  VlaserChainDownArgs a = {x, ldx, W, res, h_out, M, N, K, nullptr};
-  const VlaserCohostGuest g = {VL_GUEST_CHAIN_DOWN, &a};
-  ChainDownP p;
-  int wgs;
-  if (!vl_cohost_chain_down4(&g, VL_GUEST_CHAIN_DOWN, &p, &wgs)) {
-    if (chain_down_prepare(x, ldx, W, nullptr, res, h_out, M, N, K, nullptr, false, p)) return -1;      // (its message)
-    vlaser_set_error("vlaser_chain_down_looped: built for 5..8 rows, 3-column units, a workgroup count that 4 divides (got M %d N %d)", M, N);
-    return -1;
-  }
-  hipLaunchKernelGGL((chain_down_loop_kernel<7, 10, 2, 3, 1, GuestChainDown4::UNITS>), dim3(wgs), dim3(7 * 64), 0, (hipStream_t)s, p);
-  VL_LAUNCH_CHECK();
-  return 0;
+  return chain_down_looped<false>(x, ldx, W, nullptr, res, h_out, M, N, K, s);
 }
-/* the same for vlaser_chain_down_w8 (W = ops.pack_down4_e4m3, w_scale = ops.pack_down4_scales): the looped W8 kernel on its own, vlaser_chain_down_w8's bits */
 extern "C" int vlaser_chain_down_looped_w8(const void* x, int ldx, const void* W, const float* w_scale, const void* res, void* h_out, int M, int N, int K, vl_stream_t s) {
-  VlaserChainDownW8Args a = {x, ldx, W, res, h_out, M, N, K, nullptr, w_scale};
-  const VlaserCohostGuest g = {VL_GUEST_CHAIN_DOWN_W8, &a};
-  ChainDownP p;
-  int wgs;
-  if (!vl_cohost_chain_down4(&g, VL_GUEST_CHAIN_DOWN_W8, &p, &wgs)) {
-    if (chain_down_prepare(x, ldx, W, w_scale, res, h_out, M, N, K, nullptr, true, p)) return -1;      // (its message: null or misaligned scales among them)
-    vlaser_set_error("vlaser_chain_down_looped_w8: built for 5..8 rows, 3-column units, a workgroup count that 4 divides (got M %d N %d)", M, N);
-    return -1;
-  }
-  hipLaunchKernelGGL((chain_down_loop_kernel<7, 10, 2, 3, 1, GuestChainDown4W8::UNITS, true>), dim3(wgs), dim3(7 * 64), 0, (hipStream_t)s, p);
-  VL_LAUNCH_CHECK();
-  return 0;
+  return chain_down_looped<true>(x, ldx, W, w_scale, res, h_out, M, N, K, s);
 }
 VL_INTERNAL int vl_cohost_guest_launch(const VlaserCohostGuest* g, vl_stream_t s) {
   if (!g || g->kind == VL_GUEST_NONE) return 0;
@@ -390,14 +388,12 @@ VL_INTERNAL int vl_cohost_guest_launch(const VlaserCohostGuest* g, vl_stream_t s
     case VL_GUEST_CHAIN_ATTN: return vlaser_chain_attn((const VlaserAttnArgs*)g->args, s);
     case VL_GUEST_CHAIN_OPROJ: return vlaser_chain_oproj((const VlaserSkinnyArgs*)g->args, s);
     case VL_GUEST_CHAIN_GU: return vlaser_chain_gu((const VlaserSkinnyArgs*)g->args, s);
-    case VL_GUEST_CHAIN_DOWN: {
-      const VlaserChainDownArgs* a = (const VlaserChainDownArgs*)g->args;
-      return vlaser_chain_down(a->x, a->ldx, a->W, a->res, a->h_out, a->M, a->N, a->K, a->dbg, s);
-    }
     case VL_GUEST_CHAIN_GU_W8: return vlaser_chain_gu_w8((const VlaserSkinnyArgs*)g->args, s);
+    case VL_GUEST_CHAIN_DOWN:
     case VL_GUEST_CHAIN_DOWN_W8: {
-      const VlaserChainDownW8Args* a = (const VlaserChainDownW8Args*)g->args;
-      return vlaser_chain_down_w8(a->x, a->ldx, a->W, a->w_scale, a->res, a->h_out, a->M, a->N, a->K, a->dbg, s);
+      const VlaserChainDownArgs* a; bool w8; const float* w_scale;
+      chain_down_guest(g, &a, &w8, &w_scale);
+      return chain_down_entry(a->x, a->ldx, a->W, w_scale, a->res, a->h_out, a->M, a->N, a->K, a->dbg, s, w8);
     }
     default: break;
   }

@@ -46,25 +46,13 @@ __device__ __forceinline__ void chain_gu_body(const ChainGuP& p, const int wg) {
 #define VL_GRID_X 1
 #define VL_GRID_Y 1
 #include "chain_gu.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 template <int NS, int UE, int SP, int CPT, int TPU, bool DBG, bool W8 = false>
 __global__ __launch_bounds__(512) void chain_gu_kernel(ChainGuP p) {
-#define VL_WG_X blockIdx.x
-#define VL_WG_Y blockIdx.y
-#define VL_WG_Z blockIdx.z
-#define VL_GRID_X gridDim.x
-#define VL_GRID_Y gridDim.y
+#include "wg_bind.inc"
 #include "chain_gu.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 
 // ------------------------------------------------------------------------------------------------------------------ q / k / v
@@ -91,25 +79,13 @@ __device__ __forceinline__ void chain_qkv_body(const ChainQkvP& p, const int uni
 #define VL_GRID_X 1
 #define VL_GRID_Y 1
 #include "chain_qkv.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 template <int KS, int RG, int NWV, bool DBG>
 __global__ __launch_bounds__(64 * NWV) void chain_qkv_kernel(ChainQkvP p) {
-#define VL_WG_X blockIdx.x
-#define VL_WG_Y blockIdx.y
-#define VL_WG_Z blockIdx.z
-#define VL_GRID_X gridDim.x
-#define VL_GRID_Y gridDim.y
+#include "wg_bind.inc"
 #include "chain_qkv.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 
 // ------------------------------------------------------------------------------------------------------------------ down projection
@@ -138,25 +114,13 @@ __device__ __forceinline__ void chain_down_body(const ChainDownP& p, const int w
 #define VL_GRID_X 1
 #define VL_GRID_Y 1
 #include "chain_down.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 template <int NW, int NL, int RG, int COLS, int CG, bool DBG, bool W8 = false>
 __global__ __launch_bounds__(NW * 64) void chain_down_kernel(ChainDownP p) {
-#define VL_WG_X blockIdx.x
-#define VL_WG_Y blockIdx.y
-#define VL_WG_Z blockIdx.z
-#define VL_GRID_X gridDim.x
-#define VL_GRID_Y gridDim.y
+#include "wg_bind.inc"
 #include "chain_down.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 
 // The looped form (chain_down_loop.inc): workgroup wg does the work of the stand-alone launch's workgroups wg * UNITS .. + UNITS - 1 -- the activation slices, which
@@ -167,13 +131,13 @@ template <int NW, int NL, int RG, int COLS, int CG, int UNITS, bool W8 = false>
 __device__ __forceinline__ void chain_down_loop_body(const ChainDownP& p, const int wg) {
 #define VL_WG_X wg
 #include "chain_down_loop.inc"
-#undef VL_WG_X
+#include "wg_unbind.inc"
 }
 template <int NW, int NL, int RG, int COLS, int CG, int UNITS, bool W8 = false>
 __global__ __launch_bounds__(NW * 64) void chain_down_loop_kernel(ChainDownP p) {      // the looped body on its own (vlaser_chain_down_looped / _looped_w8: tests, tools)
-#define VL_WG_X blockIdx.x
+#include "wg_bind.inc"
 #include "chain_down_loop.inc"
-#undef VL_WG_X
+#include "wg_unbind.inc"
 }
 
 // ------------------------------------------------------------------------------------------------------------------ attention over the KV cache, <= 16 query tokens
@@ -206,25 +170,13 @@ __device__ __forceinline__ void chain_attn_body(const ChainAttnP& p, const int b
 #define VL_GRID_X gx
 #define VL_GRID_Y gy
 #include "chain_attn.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 template <int NC, int QT, bool DBG, bool DENSE = false>
 __global__ __launch_bounds__(64) void chain_attn_kernel(ChainAttnP p) {
-#define VL_WG_X blockIdx.x
-#define VL_WG_Y blockIdx.y
-#define VL_WG_Z blockIdx.z
-#define VL_GRID_X gridDim.x
-#define VL_GRID_Y gridDim.y
+#include "wg_bind.inc"
 #include "chain_attn.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 
 // ------------------------------------------------------------------------------------------------------------------ o_proj: merge of the attention splits -> GEMV -> split-K slabs
@@ -245,25 +197,13 @@ __device__ __forceinline__ void chain_oproj_body(const ChainOprojP& p, const int
 #define VL_GRID_X gx
 #define VL_GRID_Y 1
 #include "chain_oproj.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 template <int NS, int S, bool DBG>
 __global__ __launch_bounds__(512) void chain_oproj_kernel(ChainOprojP p) {
-#define VL_WG_X blockIdx.x
-#define VL_WG_Y blockIdx.y
-#define VL_WG_Z blockIdx.z
-#define VL_GRID_X gridDim.x
-#define VL_GRID_Y gridDim.y
+#include "wg_bind.inc"
 #include "chain_oproj.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 
 // ------------------------------------------------------------------------------------------------------------------ co-hosted launches: the guest side
@@ -339,13 +279,14 @@ struct GuestChainQkv {
 
 // host side (csrc/chain.hip); internal to the library: hidden, not part of the C ABI
 #define VL_INTERNAL __attribute__((visibility("hidden")))
-// (the gate/up and down preparations take the guest kind they are asked for: the bf16 kinds or their e4m3 counterparts VL_GUEST_CHAIN_GU_W8 / _DOWN_W8)
-VL_INTERNAL int vl_cohost_chain_gu(const VlaserCohostGuest* g, int kind, ChainGuP* p, int* wgs, int* lds);
+// (the gate/up and down preparations accept either kind of their launch and return 0 = not hostable here, 1 = the bf16 kind, 2 = its e4m3 counterpart VL_GUEST_CHAIN_GU_W8 /
+// _DOWN_W8: the host picks the Guest... or Guest...W8 instantiation from the answer; the others return 0 / 1)
+VL_INTERNAL int vl_cohost_chain_gu(const VlaserCohostGuest* g, ChainGuP* p, int* wgs, int* lds);
 VL_INTERNAL int vl_cohost_chain_qkv(const VlaserCohostGuest* g, ChainQkvP* p, int* units, int* lds_unit);
 VL_INTERNAL int vl_cohost_chain_attn(const VlaserCohostGuest* g, ChainAttnP* p, int* waves);
 VL_INTERNAL int vl_cohost_chain_oproj(const VlaserCohostGuest* g, ChainOprojP* p, int* wgs, int* lds);
-VL_INTERNAL int vl_cohost_chain_down(const VlaserCohostGuest* g, int kind, ChainDownP* p, int* wgs);
-VL_INTERNAL int vl_cohost_chain_down4(const VlaserCohostGuest* g, int kind, ChainDownP* p, int* wgs);      // the looped form: *wgs = workgroups of four units
+VL_INTERNAL int vl_cohost_chain_down(const VlaserCohostGuest* g, ChainDownP* p, int* wgs);
+VL_INTERNAL int vl_cohost_chain_down4(const VlaserCohostGuest* g, ChainDownP* p, int* wgs);      // the looped form: *wgs = workgroups of four units
 VL_INTERNAL int vl_cohost_guest_launch(const VlaserCohostGuest* g, vl_stream_t s);      // the guest on its own, behind its host: what every pair without a fused instantiation does
 VL_INTERNAL void vl_cohost_count_fused();          // one more launch that carried its guest (vlaser_cohost_fused_count)
 VL_INTERNAL bool vl_cohost_lab_zero_guests();      // vlaser_cohost_lab(1): fused kernels launched with no guest workgroups

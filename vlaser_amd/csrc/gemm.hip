@@ -822,27 +822,15 @@ __device__ __forceinline__ void gemm_glds_body(const GemmP& p, const int bx, con
 #define VL_GRID_X gx
 #define VL_GRID_Y gridDim.y
 #include "gemm_glds.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 
 template <int EPI, int BM, int BNT, int WM, int WN, int NST, bool WKM = false, bool AKM = false, bool IFIRST = GLDS_ISSUE_FIRST != 0, bool ASYM = false, bool SPREAD = false,
           bool PIPE = false>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmP p) {
-#define VL_WG_X blockIdx.x
-#define VL_WG_Y blockIdx.y
-#define VL_WG_Z blockIdx.z
-#define VL_GRID_X gridDim.x
-#define VL_GRID_Y gridDim.y
+#include "wg_bind.inc"
 #include "gemm_glds.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 
 // Co-hosted launch (csrc/chain_kernels.h): the host's grid, its x extent lengthened by the guest's workgroups.  Workgroups bx < host_grid are the GEMM's (tile index and
@@ -1136,23 +1124,21 @@ static int launch(const VlaserGemmArgs* args, hipStream_t stream, const VlaserCo
     if (guest && hosted && nb == 1) {
       if constexpr (EPI == VL_EPI_QKV_ROPE) {
         ChainDownP gp; int wgs;
-        if (bm == 1564 && blocks(64, 64) <= 192 && vl_cohost_chain_down4(guest, VL_GUEST_CHAIN_DOWN, &gp, &wgs)) {
-          *hosted = 1;
-          return launch_glds_cohost<GuestChainDown4, EPI, 64, 64, 2, 2, 8, PIPE>(args, stream, splits, gp, wgs, 0);
-        }
-        if (bm == 1564 && blocks(64, 64) <= 192 && vl_cohost_chain_down4(guest, VL_GUEST_CHAIN_DOWN_W8, &gp, &wgs)) {      // an 'mlp8' expert: the looped W8 body
-          *hosted = 1;
-          return launch_glds_cohost<GuestChainDown4W8, EPI, 64, 64, 2, 2, 8, PIPE>(args, stream, splits, gp, wgs, 0);
+        if (bm == 1564 && blocks(64, 64) <= 192) {
+          if (const int fmt = vl_cohost_chain_down4(guest, &gp, &wgs)) {      // (1: bf16; 2: an 'mlp8' expert, the looped W8 body)
+            *hosted = 1;
+            return fmt == 1 ? launch_glds_cohost<GuestChainDown4, EPI, 64, 64, 2, 2, 8, PIPE>(args, stream, splits, gp, wgs, 0)
+                            : launch_glds_cohost<GuestChainDown4W8, EPI, 64, 64, 2, 2, 8, PIPE>(args, stream, splits, gp, wgs, 0);
+          }
         }
       } else if constexpr (EPI == VL_EPI_SWIGLU) {
         ChainGuP gp; int wgs, lds;
-        if (bm == 1200 && vl_cohost_chain_gu(guest, VL_GUEST_CHAIN_GU, &gp, &wgs, &lds)) {
-          *hosted = 1;
-          return launch_glds_cohost<GuestChainGu, EPI, 128, 256, 2, 4, 3, SPREAD>(args, stream, splits, gp, wgs, lds);
-        }
-        if (bm == 1200 && vl_cohost_chain_gu(guest, VL_GUEST_CHAIN_GU_W8, &gp, &wgs, &lds)) {
-          *hosted = 1;
-          return launch_glds_cohost<GuestChainGuW8, EPI, 128, 256, 2, 4, 3, SPREAD>(args, stream, splits, gp, wgs, lds);
+        if (bm == 1200) {
+          if (const int fmt = vl_cohost_chain_gu(guest, &gp, &wgs, &lds)) {
+            *hosted = 1;
+            return fmt == 1 ? launch_glds_cohost<GuestChainGu, EPI, 128, 256, 2, 4, 3, SPREAD>(args, stream, splits, gp, wgs, lds)
+                            : launch_glds_cohost<GuestChainGuW8, EPI, 128, 256, 2, 4, 3, SPREAD>(args, stream, splits, gp, wgs, lds);
+          }
         }
       } else {
         ChainAttnP gp; int waves;

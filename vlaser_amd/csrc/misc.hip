@@ -1260,28 +1260,16 @@ __device__ __forceinline__ void reduce_norm_exact_body(const bf16_t* __restrict_
 #define VL_GRID_X 1
 #define VL_GRID_Y 1
 #include "reduce_norm_exact.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 template <int NORM, int NCH, int SX, bool BL>
 __global__ __launch_bounds__(64) void reduce_norm_exact_kernel(const bf16_t* __restrict__ h_in, const float* __restrict__ partials,
                                                                 const bf16_t* __restrict__ bias, const bf16_t* __restrict__ ls,
                                                                 const bf16_t* __restrict__ nw, const bf16_t* __restrict__ nb, float eps,
                                                                 bf16_t* __restrict__ h_out, bf16_t* __restrict__ x_out, int M) {
-#define VL_WG_X blockIdx.x
-#define VL_WG_Y blockIdx.y
-#define VL_WG_Z blockIdx.z
-#define VL_GRID_X gridDim.x
-#define VL_GRID_Y gridDim.y
+#include "wg_bind.inc"
 #include "reduce_norm_exact.inc"
-#undef VL_WG_X
-#undef VL_WG_Y
-#undef VL_WG_Z
-#undef VL_GRID_X
-#undef VL_GRID_Y
+#include "wg_unbind.inc"
 }
 
 // Co-hosted seam (csrc/chain_kernels.h): the seam's rows HR to a workgroup of the GUEST's block size (a row is wave-local: packing changes no bits; the other waves
@@ -1391,8 +1379,8 @@ extern "C" int vlaser_reduce_norm_cohost(const void* h_in, const float* partials
       if (vl_cohost_chain_oproj(guest, &gp, &wgs, &lds)) return launch_reduce_norm_cohost<GuestChainOproj, 3>(h, gp, wgs, lds, (hipStream_t)s);
     } else {
       ChainDownP gp;
-      if (vl_cohost_chain_down(guest, VL_GUEST_CHAIN_DOWN, &gp, &wgs)) return launch_reduce_norm_cohost<GuestChainDown, 7>(h, gp, wgs, 0, (hipStream_t)s);
-      if (vl_cohost_chain_down(guest, VL_GUEST_CHAIN_DOWN_W8, &gp, &wgs)) return launch_reduce_norm_cohost<GuestChainDownW8, 7>(h, gp, wgs, 0, (hipStream_t)s);
+      if (const int fmt = vl_cohost_chain_down(guest, &gp, &wgs))
+        return fmt == 1 ? launch_reduce_norm_cohost<GuestChainDown, 7>(h, gp, wgs, 0, (hipStream_t)s) : launch_reduce_norm_cohost<GuestChainDownW8, 7>(h, gp, wgs, 0, (hipStream_t)s);
     }
   }
   if (int rc = vlaser_reduce_norm(h_in, partials, S, bias, ls, norm_kind, nw, nb, eps, h_out, x_out, M, C, s)) return rc;

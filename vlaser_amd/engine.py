@@ -1,7 +1,8 @@
 """Kernel sequencing for the three hot loops: InternViT tile encoder, Qwen2.5 prefill / greedy
 decode, and the pi0 joint prefill + 10-step Euler sampler.  Every arithmetic step is a launch of a gfx950 kernel
 from libvlaser_hip.so through vlaser_amd.ops; PyTorch only owns buffers and the stream.  All launches are
-asynchronous and allocation-free after construction, so whole phases can be captured in one HIP graph.
+asynchronous and allocation-free after construction, so whole phases can be captured in one HIP graph.  A <= 16-row layer is a plan (_build_plan): one argument
+struct and one (name, launch, args) entry per launch, its kernel path from layer_path and its MLP weight format from ops.chain_format.
 
 Weights are stored in HBM in the layouts the kernels want (packed once at load):
   * q/k/v fused into one [N,K] matrix with in-head row permutation (RoPE pair in one MFMA lane),
@@ -117,7 +118,8 @@ def path_geometry(llm: LLMConfig, opts):
 def layer_path(*, chain_packed, H, I, n_qkv, n_gu, tpu_gu, n_o, tpu_o, ks_o, nq, nkv, hd, act_width, M, tok_per_batch, kv_len, n_partials=0, input_is_hB=False,
                skip_post_attn=False, dense_mask=False, mlp8=False):
     """(chain, chain_ao) of one skinny_layer call -- the ONE place that decides between the kernels of csrc/chain.hip and of csrc/skinny.hip (and the only caller of
-    the library's *_supported predicates).  Integers and booleans in (path_geometry of the stack + the call), no tensors.
+    the library's *_supported predicates; those of the MLP through ops.chain_format, the one place that knows the weight formats).  Integers and booleans in
+    (path_geometry of the stack + the call), no tensors.
     chain: q/k/v, gate/up and down on the latency-built kernels -- the layer takes a residual stream that is already reduced (n_partials == 0: the action encoder's output,
     or what the previous layer's vlaser_chain_down published; not hB, which this layer's gate/up launch overwrites while its other workgroups still read their input) and hands
     on (hC, None, 0).
@@ -125,11 +127,8 @@ def layer_path(*, chain_packed, H, I, n_qkv, n_gu, tpu_gu, n_o, tpu_o, ks_o, nq,
     A dense additive mask (ABI 8) is served by the chain attention only (every <= 16-row launch of the VLA at its shipped widths): NotImplementedError elsewhere.
     mlp8: the stack holds its MLP weights as e4m3 codes, which only the W8 forms of the chain gate/up and down kernels read: chain means those two launches, and a call
     that would run the MLP off the chain path raises NotImplementedError (a call that stops after q/k/v reads no MLP weight)."""
-    if mlp8:          # the gate/up W8 form has one predicate per K (hidden 1536: M <= 8)
-        gu_w8_supported = ops.chain_gu_w8_k1536_supported if H == 1536 else ops.chain_gu_w8_supported
-        mlp_ok = gu_w8_supported(M, n_gu, H, ks_o, tpu_gu) and ops.chain_down_w8_supported(M, H, I)
-    else:
-        mlp_ok = ops.chain_gu_supported(M, n_gu, H, ks_o, tpu_gu) and ops.chain_down_supported(M, H, I)
+    fmt = ops.chain_format('e4m3' if mlp8 else 'bf16', H)
+    mlp_ok = fmt.gu_supported(M, n_gu, H, ks_o, tpu_gu) and fmt.down_supported(M, H, I)
     chain = chain_packed and act_width == I and n_partials == 0 and not input_is_hB and ops.chain_qkv_supported(M, n_qkv, H) and mlp_ok
     if mlp8 and not chain and not skip_post_attn:
         raise NotImplementedError("'mlp8' (e4m3 MLP weights) needs the chain path: hidden 768 (<= 16 rows) / 1536 (<= 8 rows), MLP width 8960, an already reduced residual stream")
@@ -447,46 +446,23 @@ def skinny_layer_plan(stack, lw, sb, h_in, partials, n_partials, cache, layer, r
     return plan
 
 
-_GUEST_KINDS = {'qkv': L.GUEST_CHAIN_QKV, 'attn': L.GUEST_CHAIN_ATTN, 'o': L.GUEST_CHAIN_OPROJ, 'gu': L.GUEST_CHAIN_GU, 'down': L.GUEST_CHAIN_DOWN}
-_GUEST_KINDS_W8 = {'gu': L.GUEST_CHAIN_GU_W8, 'down': L.GUEST_CHAIN_DOWN_W8}      # the MLP launches of an 'mlp8' plan (e4m3 weights); the other three read no MLP weight
-
-
 def plan_guest(plan, name):
-    """Launch `name` of a chain plan (chain and chain_ao) as the guest descriptor of a co-hosted launch; built once per plan.  It points at the plan's own
-    argument struct, so what skinny_layer_plan brings up to date is what the host's launch reads.  The gate/up and down launches of an 'mlp8' plan become the W8 kinds:
-    gate/up on the plan's own struct (it carries w_scale), down on a struct of the operands its launch was planned with (the layer's codes and packed scales)."""
+    """Launch `name` of a chain plan (chain and chain_ao) as the guest descriptor of a co-hosted launch; built once per plan.  Its kind is the plan's weight format's
+    (ops.chain_format: the gate/up and down launches of an 'mlp8' plan are the W8 kinds); it points at the plan's own argument struct for `name`, so what skinny_layer_plan
+    brings up to date is what the host's launch reads (a struct whose `dbg` is set is refused by the fused path and runs host-then-guest)."""
     g = plan.guests.get(name)
     if g is None:
         assert plan.chain and plan.chain_ao
-        launch, args = next((l, a) for n, l, a in plan.launches if n == name)
-        kind = _GUEST_KINDS[name]
-        if name == 'down' and launch is _chain_down_w8:
-            sb, lw, M, H, I, _ = args
-            kind, a = _GUEST_KINDS_W8[name], ops.chain_down_w8_args(sb.act, lw.down8, lw.down8_scale, sb.hB, sb.hC, M, H, I)
-        elif name == 'down':
-            assert launch is _chain_down
-            sb, W4, M, H, I, _ = args
-            a = ops.chain_down_args(sb.act, W4, sb.hB, sb.hC, M, H, I)
-        else:
-            if name == 'gu' and launch is not ops.launch_chain_gu:
-                assert launch is ops.launch_chain_gu_w8          # (the K = 1536 form belongs to the greedy decode, which has no joint prefill)
-                kind = _GUEST_KINDS_W8[name]
-            a = args[0]
-        g = plan.guests[name] = ops.cohost_guest(kind, a)
+        kind, a = plan.format.guests[name], getattr(plan, name)
+        assert kind is not None, (name, 'has no guest form in this weight format')
+        g = plan.guests[name] = ops.cohost_guest(kind, a[0] if isinstance(a, tuple) else a)
     return g
-
-
-def _chain_down_w8(sb, lw, M, H, I, down, stream):
-    ops.chain_down_w8(sb.act, lw.down8, lw.down8_scale, sb.hB, sb.hC, M, H, I, dbg=down.dbg, stream=stream)
-
-
-def _chain_down(sb, W4, M, H, I, down, stream):          # `down.dbg`: read at launch time, tools set it after the plan is built
-    ops.chain_down(sb.act, W4, sb.hB, sb.hC, M, H, I, dbg=down.dbg, stream=stream)
 
 
 def _build_plan(stack, lw, sb, h_in, partials, n_partials, cache, layer, rope, pos_ids, batch, tok_per_batch, slot_base, kv_len, attn_mode, valid_len, blk_start,
                 skip_post_attn, first_tok_kv_len, dense_mask):
-    """The plan of one skinny_layer key: .chain / .chain_ao (layer_path), the argument structs .qkv / .attn / .o / .gu / .down (tools set their `dbg`), .launches =
+    """The plan of one skinny_layer key: .chain / .chain_ao (layer_path), .format (ops.chain_format of the stack's MLP weights), the argument structs .qkv / .attn / .o / .gu / .down
+    (every launch has one; tools set their `dbg`, read at launch time), .launches =
     [(name, launch, args)] in launch order, run as launch(*args, stream) (tuples, not closures over the plan: a cleared cache frees its plans at once), .result = the (h, partials, n_partials) the layer hands on.
     (The two fused launches of r03 / r04 -- o_proj -> gate/up with an in-launch hand-off, attention + o_proj in one launch -- lost to the r05 chain kernels and were
     removed from the library: DESIGN.md section 3)"""
@@ -499,7 +475,8 @@ def _build_plan(stack, lw, sb, h_in, partials, n_partials, cache, layer, rope, p
     if dense_mask is not None:
         attn_mode = L.ATTN_DENSE
     ks, vs = cache.strides()
-    plan = SimpleNamespace(chain=chain, chain_ao=chain_ao, guests={})
+    mlp8 = stack.path['mlp8']          # (layer_path has raised if the MLP of an 'mlp8' stack would leave the chain path)
+    plan = SimpleNamespace(chain=chain, chain_ao=chain_ao, format=ops.chain_format('e4m3' if mlp8 else 'bf16', H), guests={})
     plan.qkv = ops.skinny_args(h_in, lw.sk_qkv, M, partials=partials, n_partials=n_partials, norm_w=lw.ln_in, eps=llm.rms_norm_eps,
                                h_out=sb.hA, bias=lw.bqkv_sk, q_out=sb.q, k_cache=cache.k[layer], vt_cache=cache.vt[layer], rope_cos=rope[0],
                                rope_sin=rope[1], pos_ids=pos_ids, n_q_heads=nq, n_kv_heads=nkv, s_max=cache.s_max,
@@ -521,15 +498,11 @@ def _build_plan(stack, lw, sb, h_in, partials, n_partials, cache, layer, rope, p
         plan.o = ops.skinny_args(None, lw.sk_o, M, out_f32=sb.part_o, attn_m=sb.attn_parts[0], attn_l=sb.attn_parts[1],
                                  attn_o=sb.attn_parts[2], attn_splits=1, attn_group=nq // nkv, attn_nq=tok_per_batch)
         plan.launches += [('attn', ops.launch_attn_skinny, (plan.attn,)), ('o', ops.launch_skinny, (L.PRO_ATTN, L.SK_PARTIAL, plan.o[0]))]
-    mlp8 = stack.path['mlp8']          # (layer_path has raised if the MLP of an 'mlp8' stack would leave the chain path)
     plan.gu = ops.skinny_args(h_in if chain else sb.hA, lw.gu8 if mlp8 else lw.sk_gu, M, partials=sb.part_o, n_partials=stack.ks_o, norm_w=lw.ln_post,
                               eps=llm.rms_norm_eps, h_out=sb.hB, out=sb.act, ldo=sb.act.shape[1])
     if chain:
-        plan.down = SimpleNamespace(dbg=None)
-        if mlp8:
-            plan.launches += [('gu', ops.launch_chain_gu_w8_k1536 if H == 1536 else ops.launch_chain_gu_w8, (plan.gu[0],)), ('down', _chain_down_w8, (sb, lw, M, H, I, plan.down))]
-        else:
-            plan.launches += [('gu', ops.launch_chain_gu, (plan.gu[0],)), ('down', _chain_down, (sb, lw.sk_down4, M, H, I, plan.down))]
+        plan.down = ops.chain_down_args(sb.act, lw.down8 if mlp8 else lw.sk_down4, sb.hB, sb.hC, M, H, I, lw.down8_scale if mlp8 else None)
+        plan.launches += [('gu', plan.format.launch_gu, (plan.gu[0],)), ('down', ops.launch_chain_down, (plan.down,))]
         plan.result = (sb.hC, None, 0)
     else:
         plan.down = ops.skinny_args(sb.act, lw.sk_down, M, out_f32=sb.part_d)

@@ -1,5 +1,8 @@
 """Thin torch-tensor wrappers over the C ABI (include/vlaser_hip.h).  PyTorch is plumbing here: it owns device
-memory and the stream; every op below is a launch of a hand-written gfx950 kernel in libvlaser_hip.so."""
+memory and the stream; every op below is a launch of a hand-written gfx950 kernel in libvlaser_hip.so.
+A launch that a plan repeats has three forms: NAME_args(tensors) -> ctypes struct (keeps its tensors alive), launch_NAME(struct, stream), and NAME(tensors) = build
+args, launch.  The weight format of the chain MLP (bf16 / e4m3) is decided in one table, CHAIN_FORMATS."""
+import collections
 import ctypes
 import ctypes as C
 import math
@@ -131,7 +134,7 @@ def gemm(epi, A, W, out=None, bias=None, res=None, ls=None, N=None, **kw):
 
 
 def cohost_guest(kind, args):
-    """Guest descriptor of a co-hosted launch: kind = L.GUEST_*, args = the guest's own ctypes argument struct (SkinnyArgs / AttnArgs / ChainDownArgs / ChainDownW8Args), read when the
+    """Guest descriptor of a co-hosted launch: kind = L.GUEST_*, args = the guest's own ctypes argument struct (SkinnyArgs / AttnArgs / chain_down_args), read when the
     host is launched.  The descriptor keeps the struct alive."""
     g = L.CohostGuest()
     g.kind, g.args = kind, C.addressof(args)
@@ -139,20 +142,19 @@ def cohost_guest(kind, args):
     return g
 
 
-def chain_down_args(x, W4, res, h_out, M, N, K):
-    """vlaser_chain_down's arguments as a struct (the guest of a co-hosted seam)."""
+def chain_down_args(x, W, res, h_out, M, N, K, scale4=None):
+    """The chain down projection's arguments as a struct: ChainDownArgs (W = pack_down4(w), bf16), or with scale4 = pack_down4_scales(scale) ChainDownW8Args
+    (W = pack_down4_e4m3(codes)).  What launch_chain_down / launch_chain_down_looped launch and what a co-hosted launch carries as its guest; `dbg` (a stamp buffer's
+    address) may be set afterwards and is read at launch time.  The struct keeps its tensors alive."""
     assert x.dtype == BF16 and res.dtype == BF16 and h_out.dtype == BF16 and x.stride(-1) == 1 and res.data_ptr() != h_out.data_ptr()
-    a = L.ChainDownArgs()
-    a.x, a.ldx, a.W, a.res, a.h_out, a.M, a.N, a.K = x.data_ptr(), x.stride(0), W4.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K
-    return a
-
-
-def chain_down_w8_args(x, W8, scale4, res, h_out, M, N, K):
-    """vlaser_chain_down_w8's arguments as a struct (the guest of a co-hosted launch of an 'mlp8' expert)."""
-    assert x.dtype == BF16 and res.dtype == BF16 and h_out.dtype == BF16 and x.stride(-1) == 1 and res.data_ptr() != h_out.data_ptr()
-    assert W8.dtype == torch.uint8 and scale4.dtype == torch.float32 and scale4.is_contiguous()
-    a = L.ChainDownW8Args()
-    a.x, a.ldx, a.W, a.res, a.h_out, a.M, a.N, a.K, a.w_scale = x.data_ptr(), x.stride(0), W8.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K, scale4.data_ptr()
+    if scale4 is None:
+        a = L.ChainDownArgs()
+    else:
+        assert W.dtype == torch.uint8 and scale4.dtype == torch.float32 and scale4.is_contiguous()
+        a = L.ChainDownW8Args()
+        a.w_scale = scale4.data_ptr()
+    a.x, a.ldx, a.W, a.res, a.h_out, a.M, a.N, a.K = x.data_ptr(), x.stride(0), W.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K
+    a._keep = (x, W, res, h_out, scale4)
     return a
 
 
@@ -515,10 +517,7 @@ def launch_chain_gu_w8_k1536(a, stream=None):
 
 def chain_down_w8(x, W8, scale4, res, h_out, M, N, K, dbg=None, stream=None):
     """h_out[M, N] = bf16(res + scale * (x[M, :K] @ codes^T)), W8 = pack_down4_e4m3(codes), scale4 = pack_down4_scales(scale)."""
-    assert x.dtype == BF16 and res.dtype == BF16 and h_out.dtype == BF16 and x.stride(-1) == 1 and res.data_ptr() != h_out.data_ptr()
-    assert W8.dtype == torch.uint8 and scale4.dtype == torch.float32 and scale4.is_contiguous()
-    L.check(L.lib().vlaser_chain_down_w8(x.data_ptr(), x.stride(0), W8.data_ptr(), scale4.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K,
-                                         dbg if isinstance(dbg, int) else _p(dbg), _stream() if stream is None else stream), 'vlaser_chain_down_w8')
+    chain_down(x, W8, res, h_out, M, N, K, dbg, stream, scale4=scale4)
 
 
 def chain_qkv_supported(M, N, K):
@@ -562,26 +561,58 @@ def launch_chain_gu(a, stream=None):
     L.check(L.lib().vlaser_chain_gu(C.byref(a), _stream() if stream is None else stream), 'vlaser_chain_gu')
 
 
-def chain_down(x, W4, res, h_out, M, N, K, dbg=None, stream=None):
-    """h_out[M, N] = bf16(res + x[M, :K] @ W^T), W4 = pack_down4(W)."""
-    assert x.dtype == BF16 and res.dtype == BF16 and h_out.dtype == BF16 and x.stride(-1) == 1 and res.data_ptr() != h_out.data_ptr()
-    L.check(L.lib().vlaser_chain_down(x.data_ptr(), x.stride(0), W4.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K, dbg if isinstance(dbg, int) else _p(dbg),
-                                      _stream() if stream is None else stream), 'vlaser_chain_down')
+def launch_chain_down(a, stream=None):
+    """vlaser_chain_down / vlaser_chain_down_w8 on a chain_down_args struct: the entry by the struct's class, a.dbg as it stands now."""
+    s = _stream() if stream is None else stream
+    if isinstance(a, L.ChainDownW8Args):
+        L.check(L.lib().vlaser_chain_down_w8(a.x, a.ldx, a.W, a.w_scale, a.res, a.h_out, a.M, a.N, a.K, a.dbg, s), 'vlaser_chain_down_w8')
+    else:
+        L.check(L.lib().vlaser_chain_down(a.x, a.ldx, a.W, a.res, a.h_out, a.M, a.N, a.K, a.dbg, s), 'vlaser_chain_down')
+
+
+def launch_chain_down_looped(a, stream=None):
+    """The same struct by the looped kernel of its weight format (four of the stand-alone launch's workgroups to one: the guest body of the co-hosted q/k/v GEMM) as a
+    launch of its own; the same bits.  The looped entries take no stamp buffer."""
+    s = _stream() if stream is None else stream
+    if isinstance(a, L.ChainDownW8Args):
+        L.check(L.lib().vlaser_chain_down_looped_w8(a.x, a.ldx, a.W, a.w_scale, a.res, a.h_out, a.M, a.N, a.K, s), 'vlaser_chain_down_looped_w8')
+    else:
+        L.check(L.lib().vlaser_chain_down_looped(a.x, a.ldx, a.W, a.res, a.h_out, a.M, a.N, a.K, s), 'vlaser_chain_down_looped')
+
+
+def chain_down(x, W4, res, h_out, M, N, K, dbg=None, stream=None, scale4=None):
+    """h_out[M, N] = bf16(res + x[M, :K] @ W^T), W4 = pack_down4(W) (with scale4: chain_down_w8).  The tensor-taking forms of this family: build args, launch."""
+    a = chain_down_args(x, W4, res, h_out, M, N, K, scale4)
+    a.dbg = dbg if dbg is None or isinstance(dbg, int) else dbg.data_ptr()
+    launch_chain_down(a, stream)
 
 
 def chain_down_looped(x, W4, res, h_out, M, N, K, stream=None):
-    """chain_down by the looped kernel (four of its workgroups to one: the guest body of the co-hosted q/k/v GEMM) as a launch of its own; the same bits."""
-    assert x.dtype == BF16 and res.dtype == BF16 and h_out.dtype == BF16 and x.stride(-1) == 1 and res.data_ptr() != h_out.data_ptr()
-    L.check(L.lib().vlaser_chain_down_looped(x.data_ptr(), x.stride(0), W4.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K, _stream() if stream is None else stream),
-            'vlaser_chain_down_looped')
+    """chain_down by the looped kernel."""
+    launch_chain_down_looped(chain_down_args(x, W4, res, h_out, M, N, K), stream)
 
 
 def chain_down_looped_w8(x, W8, scale4, res, h_out, M, N, K, stream=None):
-    """chain_down_w8 by the looped W8 kernel (the guest body of the co-hosted q/k/v GEMM under 'mlp8') as a launch of its own; the same bits."""
-    assert x.dtype == BF16 and res.dtype == BF16 and h_out.dtype == BF16 and x.stride(-1) == 1 and res.data_ptr() != h_out.data_ptr()
-    assert W8.dtype == torch.uint8 and scale4.dtype == torch.float32 and scale4.is_contiguous()
-    L.check(L.lib().vlaser_chain_down_looped_w8(x.data_ptr(), x.stride(0), W8.data_ptr(), scale4.data_ptr(), res.data_ptr(), h_out.data_ptr(), M, N, K,
-                                                _stream() if stream is None else stream), 'vlaser_chain_down_looped_w8')
+    """chain_down_w8 by the looped W8 kernel."""
+    launch_chain_down_looped(chain_down_args(x, W8, res, h_out, M, N, K, scale4), stream)
+
+
+# The ONE place that maps a weight format of the chain MLP to its library entries.  Key: (format, K), K = the hidden size where the library has an entry per K, else None
+# (chain_format falls back to it).  gu_supported / launch_gu: the gate/up predicate and launcher; down_supported: the down predicate (its launcher goes by the struct's
+# class: launch_chain_down); guests: launch name of a chain plan -> guest kind of a co-hosted launch (None: the form belongs to the greedy decode, which has no joint
+# prefill).  engine.layer_path, engine._build_plan and engine.plan_guest read this and nothing else decides the format; a third format is one more row.
+ChainFormat = collections.namedtuple('ChainFormat', 'gu_supported launch_gu down_supported guests')
+_GUESTS = {'qkv': L.GUEST_CHAIN_QKV, 'attn': L.GUEST_CHAIN_ATTN, 'o': L.GUEST_CHAIN_OPROJ, 'gu': L.GUEST_CHAIN_GU, 'down': L.GUEST_CHAIN_DOWN}
+CHAIN_FORMATS = {
+    ('bf16', None): ChainFormat(chain_gu_supported, launch_chain_gu, chain_down_supported, _GUESTS),
+    ('e4m3', None): ChainFormat(chain_gu_w8_supported, launch_chain_gu_w8, chain_down_w8_supported, {**_GUESTS, 'gu': L.GUEST_CHAIN_GU_W8, 'down': L.GUEST_CHAIN_DOWN_W8}),
+    ('e4m3', 1536): ChainFormat(chain_gu_w8_k1536_supported, launch_chain_gu_w8_k1536, chain_down_w8_supported, {**_GUESTS, 'gu': None, 'down': L.GUEST_CHAIN_DOWN_W8}),
+}
+
+
+def chain_format(weights, K):
+    """The CHAIN_FORMATS row of MLP weights 'bf16' / 'e4m3' at hidden size K."""
+    return CHAIN_FORMATS.get((weights, K)) or CHAIN_FORMATS[(weights, None)]
 
 
 # measured on the action-expert chunk: 72 / 100 / 130 / 160 target blocks -> 16.63 / 16.52 / 16.48 / 16.50 ms

@@ -162,6 +162,74 @@ def cohost_plan(hosts, guests, enabled=tuple(COHOST_PAIRS), lagged=()):
     return out
 
 
+# Euler-phase kernel options of the action expert (VLASER_EULER overrides: comma list, "none" = the r02 kernels):
+#   qkv16: 16-row lane-local units for the q/k/v weight-streaming GEMV (128 instead of 64 workgroups): -0.88 us per layer-step in-chain
+#   gu16: the same for gate/up (1120 units): +0.6 us in-chain with the r03 kernel (its five units streamed one after the other, see csrc/chain.hip) -- on again
+#         with 'chain' (r05), whose gate/up requests all five up front
+#   glue1: ONE launch between two passes through the layers (vlaser_vla_step: tail of Euler step s-1 + action encoder of step s) instead of four:
+#          10.9 vs 16.3 us in isolation, -0.085 ms per chunk in-chain (tools/micro/vla_step_lab.py, ab_chunk.py) -- ON.  Not bit-identical to the
+#          4-launch path (linear_1 / time embedding folded into linear_2 in fp32): same tolerance against oracle and goldens
+# measurements + in-kernel timelines: profiles/r03c_euler_fusion.md
+#   chain (r05, needs qkv16): q/k/v, gate/up and the down projection on the latency-built kernels of csrc/chain.hip -- every request of a launch issued up front,
+#          one wave per q/k/v unit, the down projection publishing the bf16 residual stream once (no split-K slabs for the next layer to re-reduce): ON.  Same
+#          tolerance against oracle / goldens as the skinny kernels; gate/up bit-identical, q/k/v and down sum in a different fp32 order
+#   mlp8 (opt-in, needs chain + qkv16 + gu16; also expert_mlp_weights='fp8'): the expert's gate/up/down weights stored as OCP e4m3 codes with one power-of-two
+#          scale per row, quantised at load (ops.quantize_rows_e4m3) and streamed by the W8 forms of the chain gate/up and down kernels -- half the MLP's bytes and
+#          footprint (1.16 -> 0.58 GB at full depth).  Weight-only: bf16 MFMAs and summation orders unchanged, so the chunk is bit-identical to the default path run
+#          on the dequantised weights.  It is NOT the bf16 model: on the synthetic test model the chunk moves by 1.5e-2 (the reference's own bf16 mode sits 6.5e-3 to
+#          1.6e-2 from its fp32 chunk); the deviation on released checkpoints is unmeasured.  A/B: profiles/fp8_mlp_ab.md.  OFF by default
+#   cohost (needs chain + qkv16 + gu16 + glue1; batch 1 with the proprio row riding, no general masks -- today's schedule otherwise; bf16 or 'mlp8' expert weights): the first
+#          pass through the expert (Euler step 0, the five rows that carry the proprio token) is issued INSIDE the joint prefill: expert layer l needs the prefix K / V^T
+#          of VLM layer l and its own previous layer only, so its launches ride as extra workgroups of the prefill's own launches (COHOST_PAIRS; csrc/chain_kernels.h)
+#          on the CUs their single-round grids leave idle.  One queue, no flags, no polling; bit-identical (same bodies, same summation orders).
+#          'cohost' = every pair; 'cohost=qkv+gu' = only those pairs ride, the other guests run as launches of their own behind their hosts.  profiles/cohost_ab.md
+#          ON for the four pairs that pass the per-pair A/B (tools/micro/cohost_ab.py, one model instance): qkv, attn, o, gu; hosting the down projection in the second seam
+#          is worth 0.04-0.05 ms, less than the 0.06 ms run-to-run spread of that job, and stays opt-in ('cohost' = all five)
+#          'down_next' among the pairs (not together with 'down'): the down projection of expert layer l rides in the q/k/v GEMM of VLM layer l + 1 instead
+#          (COHOST_LAGGED; 192 workgroups of one per CU leave 64 CUs idle for 12 us), run there by the looped body -- 64 workgroups of four units, the activations
+#          requested once (csrc/chain_down_loop.inc).  The fused launch lasts 12.75 us against the host's 11.97, and a 6.7 us launch leaves the chain 27 times:
+#          -0.14 ms per chunk in the set, -0.16 ms alone, against a 0.07 ms spread; bench.py 11.087 -> 10.935 ms.  ON.  profiles/cohost_lag_ab.md
+#          With 'mlp8' the expert's gate/up and down projection ride as the W8 guest kinds (the stand-alone W8 kernels' bodies, the looped W8 body in the q/k/v GEMM):
+#          bench.py 10.731 -> 10.260 ms with the five pairs named, 0.63 ms under the default model.  expert_mlp_weights='fp8' without an option string hosts the
+#          default set minus COHOST_MLP8_DEFAULT_OFF.  profiles/cohost_fp8_ab.md
+EULER_DEFAULT = 'qkv16,gu16,glue1,chain,cohost=qkv+attn+o+gu+down_next'      # (gu16 ON with chain since r05: 224 workgroups x 5 units instead of 187 x 3, 11.79 -> 11.68 ms per chunk, same-box A/B)
+
+
+def resolve_euler_opts(euler_opts=None, expert_mlp_weights='bf16', env_value=None):
+    """(opts, expert_mlp_weights, cohost_pairs, cohost_lagged) of a PiZero: the Euler options as a tuple, 'bf16' / 'fp8', the pairs of the co-hosted joint prefill that are
+    switched on (None: the option is off) and the guests that ride one VLM layer later ('down_next': COHOST_LAGGED).  Precedence: the `euler_opts` argument, then
+    env_value (the caller's os.environ.get('VLASER_EULER')), then EULER_DEFAULT.  Pure: no GPU, no library, no environment (internvl_chat.resolve_decode_opts is its
+    VLM-side counterpart)."""
+    eo = (EULER_DEFAULT if env_value is None else env_value) if euler_opts is None else euler_opts
+    opts = tuple(x for x in eo.split(',') if x and x != 'none')
+    # expert_mlp_weights='fp8' (opt-in; the same as 'mlp8' among the Euler options): see 'mlp8' above -- not the bf16 model, deviation on released checkpoints unmeasured
+    if expert_mlp_weights not in ('bf16', 'fp8'):
+        raise ValueError(f"expert_mlp_weights: 'bf16' or 'fp8', not {expert_mlp_weights!r}")
+    if expert_mlp_weights == 'fp8' and 'mlp8' not in opts:
+        opts += ('mlp8',)
+    if 'mlp8' in opts:
+        missing = [o for o in ('chain', 'qkv16', 'gu16') if o not in opts]
+        if missing:
+            raise ValueError(f"Euler option 'mlp8' (expert_mlp_weights='fp8') needs {', '.join(missing)}: the e4m3 MLP weights are read by the chain kernels' 16-row-unit forms only")
+    expert_mlp_weights = 'fp8' if 'mlp8' in opts else 'bf16'
+    if euler_opts is None and env_value is None and expert_mlp_weights == 'fp8':      # the default pair set of an mlp8 model
+        opts = tuple('cohost=' + '+'.join(x for x in o[len('cohost='):].split('+') if x not in COHOST_MLP8_DEFAULT_OFF) if o.startswith('cohost=') else o for o in opts)
+    cohost_pairs, cohost_lagged = None, ()
+    for o in opts:
+        if o == 'cohost' or o.startswith('cohost='):          # 'cohost' / 'cohost=a+b'
+            pairs = tuple(COHOST_PAIRS) if o == 'cohost' else tuple(x for x in o[len('cohost='):].split('+') if x)
+            bad = [x for x in pairs if x not in COHOST_PAIRS and x not in LAG_TOKENS]
+            missing = [x for x in ('chain', 'qkv16', 'gu16', 'glue1') if x not in opts]
+            if bad or missing:
+                raise ValueError(f"Euler option {o!r}: " + (f"unknown pair(s) {', '.join(bad)} (of {', '.join((*COHOST_PAIRS, *LAG_TOKENS))})" if bad else f"needs {', '.join(missing)}"))
+            both = [x for x in pairs if x in LAG_TOKENS and LAG_TOKENS[x] in pairs]
+            if both:
+                raise ValueError(f"Euler option {o!r}: {both[0]} and {LAG_TOKENS[both[0]]} are two places for one launch: name one of them")
+            cohost_pairs = tuple(x for x in pairs if x in COHOST_PAIRS)
+            cohost_lagged = tuple(LAG_TOKENS[x] for x in pairs if x in LAG_TOKENS)
+    return opts, expert_mlp_weights, cohost_pairs, cohost_lagged
+
+
 class _ActionChunk(torch.Tensor):
     """The tensor `infer_action` returns when it was handed the reference's dense masks: an ordinary device tensor that remembers the model whose deferred mask
     check covers it.  The check itself never synchronises (pizero.py::_poll_errors); but the first thing a caller does with a chunk is bring it to the host
@@ -190,37 +258,7 @@ class _ActionChunk(torch.Tensor):
 
 
 class PiZero:
-    # Euler-phase kernel options of the action expert (VLASER_EULER overrides: comma list, "none" = the r02 kernels):
-    #   qkv16: 16-row lane-local units for the q/k/v weight-streaming GEMV (128 instead of 64 workgroups): -0.88 us per layer-step in-chain
-    #   gu16: the same for gate/up (1120 units): +0.6 us in-chain with the r03 kernel (its five units streamed one after the other, see csrc/chain.hip) -- on again
-    #         with 'chain' (r05), whose gate/up requests all five up front
-    #   glue1: ONE launch between two passes through the layers (vlaser_vla_step: tail of Euler step s-1 + action encoder of step s) instead of four:
-    #          10.9 vs 16.3 us in isolation, -0.085 ms per chunk in-chain (tools/micro/vla_step_lab.py, ab_chunk.py) -- ON.  Not bit-identical to the
-    #          4-launch path (linear_1 / time embedding folded into linear_2 in fp32): same tolerance against oracle and goldens
-    # measurements + in-kernel timelines: profiles/r03c_euler_fusion.md
-    #   chain (r05, needs qkv16): q/k/v, gate/up and the down projection on the latency-built kernels of csrc/chain.hip -- every request of a launch issued up front,
-    #          one wave per q/k/v unit, the down projection publishing the bf16 residual stream once (no split-K slabs for the next layer to re-reduce): ON.  Same
-    #          tolerance against oracle / goldens as the skinny kernels; gate/up bit-identical, q/k/v and down sum in a different fp32 order
-    #   mlp8 (opt-in, needs chain + qkv16 + gu16; also expert_mlp_weights='fp8'): the expert's gate/up/down weights stored as OCP e4m3 codes with one power-of-two
-    #          scale per row, quantised at load (ops.quantize_rows_e4m3) and streamed by the W8 forms of the chain gate/up and down kernels -- half the MLP's bytes and
-    #          footprint (1.16 -> 0.58 GB at full depth).  Weight-only: bf16 MFMAs and summation orders unchanged, so the chunk is bit-identical to the default path run
-    #          on the dequantised weights.  It is NOT the bf16 model: on the synthetic test model the chunk moves by 1.5e-2 (the reference's own bf16 mode sits 6.5e-3 to
-    #          1.6e-2 from its fp32 chunk); the deviation on released checkpoints is unmeasured.  A/B: profiles/fp8_mlp_ab.md.  OFF by default
-    #   cohost (needs chain + qkv16 + gu16 + glue1; batch 1 with the proprio row riding, no general masks -- today's schedule otherwise; bf16 or 'mlp8' expert weights): the first
-    #          pass through the expert (Euler step 0, the five rows that carry the proprio token) is issued INSIDE the joint prefill: expert layer l needs the prefix K / V^T
-    #          of VLM layer l and its own previous layer only, so its launches ride as extra workgroups of the prefill's own launches (COHOST_PAIRS; csrc/chain_kernels.h)
-    #          on the CUs their single-round grids leave idle.  One queue, no flags, no polling; bit-identical (same bodies, same summation orders).
-    #          'cohost' = every pair; 'cohost=qkv+gu' = only those pairs ride, the other guests run as launches of their own behind their hosts.  profiles/cohost_ab.md
-    #          ON for the four pairs that pass the per-pair A/B (tools/micro/cohost_ab.py, one model instance): qkv, attn, o, gu; hosting the down projection in the second seam
-    #          is worth 0.04-0.05 ms, less than the 0.06 ms run-to-run spread of that job, and stays opt-in ('cohost' = all five)
-    #          'down_next' among the pairs (not together with 'down'): the down projection of expert layer l rides in the q/k/v GEMM of VLM layer l + 1 instead
-    #          (COHOST_LAGGED; 192 workgroups of one per CU leave 64 CUs idle for 12 us), run there by the looped body -- 64 workgroups of four units, the activations
-    #          requested once (csrc/chain_down_loop.inc).  The fused launch lasts 12.75 us against the host's 11.97, and a 6.7 us launch leaves the chain 27 times:
-    #          -0.14 ms per chunk in the set, -0.16 ms alone, against a 0.07 ms spread; bench.py 11.087 -> 10.935 ms.  ON.  profiles/cohost_lag_ab.md
-    #          With 'mlp8' the expert's gate/up and down projection ride as the W8 guest kinds (the stand-alone W8 kernels' bodies, the looped W8 body in the q/k/v GEMM):
-    #          bench.py 10.731 -> 10.260 ms with the five pairs named, 0.63 ms under the default model.  expert_mlp_weights='fp8' without an option string hosts the
-    #          default set minus COHOST_MLP8_DEFAULT_OFF.  profiles/cohost_fp8_ab.md
-    EULER_DEFAULT = 'qkv16,gu16,glue1,chain,cohost=qkv+attn+o+gu+down_next'      # (gu16 ON with chain since r05: 224 workgroups x 5 units instead of 187 x 3, 11.79 -> 11.68 ms per chunk, same-box A/B)
+    EULER_DEFAULT = EULER_DEFAULT          # (resolve_euler_opts, above, and its commentary)
 
     ERR_BITS = {1: 'image_text_proprio_mask: the keys the proprio row sees are not a contiguous valid prefix',
                 2: 'image_text_proprio_mask: a valid-prefix row (or the proprio row\'s own key) does not have the prefix pattern of build_causal_mask_and_position_ids',
@@ -255,36 +293,7 @@ class PiZero:
         # being checked against the prefix + trailing-block pattern.  Slower (every key tile is walked with its mask values);
         # the default path and its timings are untouched.  Still refused: an image / text row that sees the proprio key (ERR_BITS[8]).
         self.general_masks = bool(general_masks)
-        eo = os.environ.get('VLASER_EULER', self.EULER_DEFAULT) if euler_opts is None else euler_opts
-        self.euler_opts = tuple(x for x in eo.split(',') if x and x != 'none')
-        # expert_mlp_weights='fp8' (opt-in; the same as 'mlp8' among the Euler options): see 'mlp8' above -- not the bf16 model, deviation on released checkpoints unmeasured
-        if expert_mlp_weights not in ('bf16', 'fp8'):
-            raise ValueError(f"expert_mlp_weights: 'bf16' or 'fp8', not {expert_mlp_weights!r}")
-        if expert_mlp_weights == 'fp8' and 'mlp8' not in self.euler_opts:
-            self.euler_opts += ('mlp8',)
-        if 'mlp8' in self.euler_opts:
-            missing = [o for o in ('chain', 'qkv16', 'gu16') if o not in self.euler_opts]
-            if missing:
-                raise ValueError(f"Euler option 'mlp8' (expert_mlp_weights='fp8') needs {', '.join(missing)}: the e4m3 MLP weights are read by the chain kernels' 16-row-unit forms only")
-        self.expert_mlp_weights = 'fp8' if 'mlp8' in self.euler_opts else 'bf16'
-        if euler_opts is None and 'VLASER_EULER' not in os.environ and self.expert_mlp_weights == 'fp8':      # the default pair set of an mlp8 model
-            self.euler_opts = tuple('cohost=' + '+'.join(x for x in o[len('cohost='):].split('+') if x not in COHOST_MLP8_DEFAULT_OFF) if o.startswith('cohost=') else o
-                                    for o in self.euler_opts)
-        # 'cohost' / 'cohost=a+b': the pairs of the co-hosted joint prefill that are switched on (None: the option is off)
-        # cohost_lagged: the guests that ride one VLM layer later ('down_next': COHOST_LAGGED)
-        self.cohost_pairs, self.cohost_lagged = None, ()
-        for o in self.euler_opts:
-            if o == 'cohost' or o.startswith('cohost='):
-                pairs = tuple(COHOST_PAIRS) if o == 'cohost' else tuple(x for x in o[len('cohost='):].split('+') if x)
-                bad = [x for x in pairs if x not in COHOST_PAIRS and x not in LAG_TOKENS]
-                missing = [x for x in ('chain', 'qkv16', 'gu16', 'glue1') if x not in self.euler_opts]
-                if bad or missing:
-                    raise ValueError(f"Euler option {o!r}: " + (f"unknown pair(s) {', '.join(bad)} (of {', '.join((*COHOST_PAIRS, *LAG_TOKENS))})" if bad else f"needs {', '.join(missing)}"))
-                both = [x for x in pairs if x in LAG_TOKENS and LAG_TOKENS[x] in pairs]
-                if both:
-                    raise ValueError(f"Euler option {o!r}: {both[0]} and {LAG_TOKENS[both[0]]} are two places for one launch: name one of them")
-                self.cohost_pairs = tuple(x for x in pairs if x in COHOST_PAIRS)
-                self.cohost_lagged = tuple(LAG_TOKENS[x] for x in pairs if x in LAG_TOKENS)
+        self.euler_opts, self.expert_mlp_weights, self.cohost_pairs, self.cohost_lagged = resolve_euler_opts(euler_opts, expert_mlp_weights, os.environ.get('VLASER_EULER'))
         self._graphs = {}
         self._pos_state = None
         self._pos_next = None
